@@ -17,8 +17,15 @@ process) or `python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N`.
 
 Two throughputs: `value` is the whole step (sketch + exchange + all-pairs),
-end to end; `dist_pairs_per_s` is the metric's own quantity per SURVEY.md
-§8(d): pairs / all-pairs stage time with the sketches resident.
+end to end; `dist_pairs_per_s` (--full) is the metric's own quantity per
+SURVEY.md §8(d): pairs / all-pairs stage time with the sketches resident.
+
+A plain run sets up, warms up, times --steps steps, writes the last timed
+step's outputs when --dump-outputs DIR is given, and prints the headline line
+(metric, value, unit, ms_per_step, ...).  Everything else -- the per-kernel
+times of PROFILE_STEPS extra steps, the stage split, the rooflines, the output
+D2H leg, the oracle check of the timed outputs, --verify and the CPU baseline
+-- runs only with --full, which prints the same headline keys plus those blocks.
 """
 import argparse
 import json
@@ -159,20 +166,69 @@ def parse():
     ap.add_argument("--sketch", type=int, default=1000)
     ap.add_argument("--family-size", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0xD2E9)
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="time the C oracle on host cores (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: per-kernel "
+                         "times (extra steps), stage split, rooflines, output D2H, --check, --verify and "
+                         "--cpu-baseline (all untimed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (this rank's sketches and shared-hash "
+                         "counts) as DIR/<name>.npy, float32/float64, at most 64 MB in all (a fixed seeded "
+                         "sample of a larger array)")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="with --full: time the C oracle on host cores (rank 0)")
     ap.add_argument("--pipeline", type=int, default=1,
                     help="queue each step before checking the previous one (1) or one step at a time (0)")
     ap.add_argument("--defer-check", type=int, default=1,
                     help="check the sketch's threshold status after queuing the all-pairs (1) or before (0)")
     ap.add_argument("--check", type=int, default=1,
-                    help="after timing (untimed): check a sample of the timed steps' own sketches and "
+                    help="with --full, after timing (untimed): check a sample of the timed steps' own sketches and "
                          "shared-hash counts against the C oracle (test infrastructure); 'verified' in "
                          "the JSON line")
     ap.add_argument("--verify", type=int, default=0,
-                    help="after timing, every rank re-sketches all genomes and recomputes the whole "
-                         "triangle on its own GPU and checks its gathered sketches and its segment "
+                    help="with --full, after timing, every rank re-sketches all genomes and recomputes the "
+                         "whole triangle on its own GPU and checks its gathered sketches and its segment "
                          "(rehearsal of the sharded path; untimed)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.verify and not args.full:
+        ap.error("--verify 1 needs --full")
+    return args
+
+
+DUMP_BUDGET_BYTES = 60 << 20   # all of --dump-outputs' arrays, every rank's together (limit: 64 MB)
+
+
+def dump_sample(a, max_elems):
+    """`a` itself when it has at most max_elems elements, else a fixed sample
+    of them (1-D): sorted flat indices (repeats allowed) from a generator
+    seeded by the array's size and the sample's alone, so two runs of one
+    workload keep the same elements."""
+    if a.size <= max_elems:
+        return a
+    idx = np.sort(np.random.default_rng([a.size, max_elems]).integers(0, a.size, max_elems))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(dirname, rank, world, loc_h, loc_n, d_common, nloc, seg):
+    """What a caller of the timed path holds after its last step, this rank's
+    part: the sketch matrix (uint64 hashes, all-ones where a genome has fewer
+    than s; written as two float64 arrays of the high and low 32 bits, which
+    float64 holds exactly), the hashes per genome and the condensed shared-hash
+    counts of this rank's row range (uint16 values; float32 holds them
+    exactly).  One rank writes <name>.npy; several write <name>_rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    budget = DUMP_BUDGET_BYTES // world
+    # shares of the budget: 3/8 to each half of the hashes (f64), 1/16 to the
+    # sizes and 3/16 to the counts (f32)
+    H = dump_sample(loc_h[:nloc].cpu().numpy().view(np.uint64), budget * 3 // 8 // 8)
+    np.save(os.path.join(dirname, "sketch_hashes_hi%s.npy" % sfx), (H >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(dirname, "sketch_hashes_lo%s.npy" % sfx), (H & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    NH = dump_sample(loc_n[:nloc].cpu().numpy().view(np.uint32), budget // 16 // 4)
+    np.save(os.path.join(dirname, "sketch_sizes%s.npy" % sfx), NH.astype(np.float32))
+    C = dump_sample(d_common[:seg].cpu().numpy().view(np.uint16), budget * 3 // 16 // 4)
+    np.save(os.path.join(dirname, "shared_hash_counts%s.npy" % sfx), C.astype(np.float32))
 
 
 def config_name(N, L, s):
@@ -576,6 +632,54 @@ def main():
         stage["gather"] = 0.0
         elapsed = timed()
 
+    K = args.steps
+    ms_step = elapsed / K * 1e3
+    pairs = N * (N - 1) / 2
+    value = pairs / (elapsed / K)
+
+    # the buffers hold what the last timed step computed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, loc_h, loc_n, d_common, nloc, seg)
+
+    headline = {
+        "metric": "genome pairs/sec (mash dist, k=21 s=1000) + sketch GB/s, at 1/2/4/8 GPUs",
+        "value": value,
+        "unit": "genome pairs/s",
+        "value_kind": "end to end: N(N-1)/2 / whole step (sketch + sketch exchange + all-pairs), inputs in HBM",
+        "n_gpus": world,
+        "ranks_seen": dist.get_world_size() if world > 1 else 1,
+        "backend": (backend if world > 1 else None),
+        "rccl_version": rccl_version(torch) if world > 1 and backend == "nccl" else None,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic (on-device splitmix64 genome families, 2-bit packed; see DESIGN.md)",
+        "config": {
+            "workload": "%d synthetic %d bp genomes, k=21, s=%d (%s); step = %s"
+                        % (N, L, s, config_name(N, L, s),
+                           "sketch shard + RCCL all-gather of sketches + all-pairs row shard" if world > 1
+                           else "sketch + all-pairs (one GPU: no all-gather)"),
+            "genomes": N, "genome_bp": L, "k": 21, "sketch": s, "family_size": args.family_size,
+            "parallelism": "sketch: genome shards; all-pairs: balanced row shards; RCCL all-gather",
+            "host_loop": ("pipelined: step i+1 queued before step i's checks" if args.pipeline
+                          else "one step at a time") + (", deferred sketch check" if args.defer_check else ""),
+        },
+        "full": bool(args.full),
+        "outputs_dumped_to": args.dump_outputs,
+    }
+    if not args.full:
+        # a plain run ends here: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(headline))
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
+
     # the timed (possibly pipelined) steps' outputs, checked below (oracle
     # sample by default; --verify: the whole job recomputed on this GPU)
     snap = (loc_h.clone(), loc_n.clone(), d_common.clone()) if (args.verify or args.check) else None
@@ -593,7 +697,6 @@ def main():
     ctx.set_timing(True, kernels=(0,))
     screen = ctx.screen_stats()
 
-    K = args.steps
     # stage split per step from the kernels' HIP events (the host cannot see
     # it: sketch, gather and all-pairs are queued back to back): sketch = hash
     # kernel (timed steps) + finalize (extra steps); dist = the rest
@@ -603,9 +706,6 @@ def main():
         st = torch.tensor([stage["sketch"], stage["gather"], stage["dist"]], dtype=torch.float64, device=dev)
         dist.all_reduce(st, op=dist.ReduceOp.MAX)
         stage = dict(zip(["sketch", "gather", "dist"], st.tolist()))
-    ms_step = elapsed / K * 1e3
-    pairs = N * (N - 1) / 2
-    value = pairs / (elapsed / K)
 
     # ---- roofline of the dominant kernel (sketch hash), this rank's launches
     sk_ms, sk_n = kms[0]
@@ -697,36 +797,11 @@ def main():
         cpu = cpu_baseline(args, threads, share)
 
     if rank == 0:
-        out = {
-            "metric": "genome pairs/sec (mash dist, k=21 s=1000) + sketch GB/s, at 1/2/4/8 GPUs",
-            "value": value,
-            "unit": "genome pairs/s",
-            "value_kind": "end to end: N(N-1)/2 / whole step (sketch + sketch exchange + all-pairs), inputs in HBM",
+        out = dict(headline)
+        out.update({
             "dist_pairs_per_s": pairs / (stage["dist"] / K) if stage["dist"] else None,
             "dist_pairs_per_s_kind": "the metric's quantity (SURVEY.md 8(d)): N(N-1)/2 / all-pairs stage time "
                                      "per step, sketches resident",
-            "n_gpus": world,
-            "ranks_seen": dist.get_world_size() if world > 1 else 1,
-            "backend": (backend if world > 1 else None),
-            "rccl_version": rccl_version(torch) if world > 1 and backend == "nccl" else None,
-            "steps": K,
-            "warmup": args.warmup,
-            "ms_per_step": ms_step,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic (on-device splitmix64 genome families, 2-bit packed; see DESIGN.md)",
-            "config": {
-                "workload": "%d synthetic %d bp genomes, k=21, s=%d (%s); step = %s"
-                            % (N, L, s, config_name(N, L, s),
-                               "sketch shard + RCCL all-gather of sketches + all-pairs row shard" if world > 1
-                               else "sketch + all-pairs (one GPU: no all-gather)"),
-                "genomes": N, "genome_bp": L, "k": 21, "sketch": s, "family_size": args.family_size,
-                "parallelism": "sketch: genome shards; all-pairs: balanced row shards; RCCL all-gather",
-                "host_loop": ("pipelined: step i+1 queued before step i's checks" if args.pipeline
-                              else "one step at a time") + (", deferred sketch check" if args.defer_check else ""),
-            },
             "stages": {
                 "sketch_ms_per_step": stage["sketch"] / K * 1e3,
                 "allgather_ms_per_step": stage["gather"] / K * 1e3,
@@ -786,7 +861,7 @@ def main():
                                    if screen.get("used") else None),
             },
             "cpu_baseline": cpu,
-        }
+        })
         if checked is not None:
             out["verified"] = checked["verified"]
             out["verification"] = dict(checked, how="timed steps' outputs vs the C oracle: sampled genomes "

@@ -13,7 +13,7 @@ profiled dispatches are the screened LIST template or the dense one) and the
 library build (drephip_build_id of drep_amd/lib/libdrephip.so, loaded here
 without a GPU): bench.py quotes a profile only for its own workload and build.
 
-`calls` = all-pairs calls the profiled command made (bench.py --steps 1
+`calls` = all-pairs calls the profiled command made (bench.py --full --steps 1
 --warmup 0: 4, its three timing steps included; tools/ap_bench.py with
 AP_ITERS=1: 1).  A call over a large triangle is several dispatches (grid
 limit), so every figure is per CALL = the whole N(N-1)/2 triangle: the sum

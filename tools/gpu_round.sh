@@ -32,7 +32,7 @@ export MASTER_ADDR=127.0.0.1
 fail() { echo "step $1 failed"; [ -n "$2" ] && tail -${3:-20} "$2" | grep -v amdgpu.ids; exit 1; }
 bench_line() {   # name, args...
   local n=$1; shift
-  timeout -k 10 ${BENCH_LIMIT:-300} python bench.py "$@" > $O/$n.json 2> $O/$n.err || fail $n $O/$n.err
+  timeout -k 10 ${BENCH_LIMIT:-300} python bench.py --full "$@" > $O/$n.json 2> $O/$n.err || fail $n $O/$n.err
   python3 - $O/$n.json <<'EOF'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 R=${ROUND:-r03}
 OUT=$PWD/gpurun_out/$R
 mkdir -p $OUT
-BARGS="--check 0 --cpu-baseline 0"
+BARGS="--full --check 0 --cpu-baseline 0"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- \
     python bench.py --steps 5 --warmup 1 $BARGS > $OUT/trace_bench.json 2> $OUT/trace.err || exit 1
 KMS=$(python3 -c "

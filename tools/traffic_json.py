@@ -38,7 +38,7 @@ def main():
     print(json.dumps({
         "kernel": sorted(names)[0] if names else KERNEL,
         "build_id": _lib.build_id(),
-        "command": "rocprofv3 --pmc <C> -- python bench.py --steps 1 --warmup 0 --cpu-baseline 0 (one pass per counter)",
+        "command": "rocprofv3 --pmc <C> -- python bench.py --full --steps 1 --warmup 0 --cpu-baseline 0 (one pass per counter)",
         "dispatches": [len(f), len(w)],
         "genomes_per_launch": G,
         "bases_per_launch": G * P,
