@@ -11,7 +11,8 @@ fallback: without the HIP library every compute call raises.
 from . import mash_io
 from ._lib import Context, DrepHipError
 
-__all__ = ["Context", "DrepHipError", "mash_io", "d_cluster"]
+__all__ = ["Context", "DrepHipError", "mash_io", "d_cluster", "SparseMash", "all_vs_all_MASH_sparse",
+           "cluster_mash_sparse", "mdb_from_sparse", "store_sparse", "load_sparse"]
 __version__ = "0.1.0"
 
 
@@ -19,4 +20,10 @@ def __getattr__(name):
     if name == "d_cluster":   # lazy: pulls in pandas/scipy
         import importlib
         return importlib.import_module(".d_cluster", __name__)
+    if name in ("SparseMash", "all_vs_all_MASH_sparse", "cluster_mash_sparse", "mdb_from_sparse"):
+        import importlib           # the sparse pipeline (>~2x10^5 genomes), lazy for the same reason
+        return getattr(importlib.import_module(".d_cluster", __name__), name)
+    if name in ("store_sparse", "load_sparse"):
+        import importlib
+        return getattr(importlib.import_module(".store", __name__), name)
     raise AttributeError(name)

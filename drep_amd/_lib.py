@@ -80,6 +80,12 @@ SIGNATURES = {
     "drephip_allpairs_device_marked": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp,
                                                  C.c_uint64, vp, C.c_uint64, vp]),
     "drephip_allpairs_merge_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]),
+    "drephip_allpairs_sparse_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64,
+                                                 C.POINTER(C.c_uint64), vp]),
+    "drephip_allpairs_sparse": (C.c_int, [vp, u64p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64,
+                                          C.POINTER(C.c_uint64)]),
+    "drephip_last_sparse_stats": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64)]),
     "drephip_distance_lut": (C.c_int, [C.c_int, C.c_uint32, f64p]),
     "drephip_write_mash_table": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, vp, vp, C.c_uint32,
                                            vp, vp, u16p, f64p, C.c_int]),
@@ -589,6 +595,71 @@ class Context:
                                           common_out.ctypes.data,
                                           denom_out.ctypes.data if denom_out is not None else None),
               "drephip_allpairs_rows")
+
+    # -- sparse all-pairs (include/drephip.h: drephip_allpairs_sparse ...)
+    ERR_NOMEM = -4
+
+    def allpairs_sparse_raw(self, hashes: np.ndarray, nhash: np.ndarray, row0: int, row1: int,
+                            pairs: Optional[np.ndarray]) -> Tuple[int, int]:
+        """One drephip_allpairs_sparse call into `pairs` (uint32 [cap, 4],
+        contiguous; None: count only): (return code, records the rows hold).
+        Raises on every error but DREPHIP_ERR_NOMEM (the buffer is too small)."""
+        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+        nhash = np.ascontiguousarray(nhash, dtype=np.uint32)
+        N = len(nhash)
+        if hashes.shape != (N, self.s):
+            raise ValueError("hashes must be [N, s] = [%d, %d], got %s" % (N, self.s, hashes.shape))
+        cap = 0
+        if pairs is not None:
+            if pairs.dtype != np.uint32 or not pairs.flags.c_contiguous or pairs.ndim != 2 or pairs.shape[1] != 4:
+                raise ValueError("pairs must be a contiguous uint32 [cap, 4] array")
+            cap = len(pairs)
+        n = C.c_uint64(0)
+        rc = lib().drephip_allpairs_sparse(self._h, hashes.reshape(-1), nhash, N, int(row0), int(row1),
+                                           pairs.ctypes.data if cap else None, cap, C.byref(n))
+        if rc != self.ERR_NOMEM:
+            check(rc, "drephip_allpairs_sparse")
+        return rc, n.value
+
+    def allpairs_sparse(self, hashes: np.ndarray, nhash: np.ndarray, row0: int = 0, row1: Optional[int] = None,
+                        cap: Optional[int] = None):
+        """The pairs of rows [row0, row1) that share a hash, as (i, j, common,
+        denom) -- uint32, uint32, uint16, uint16 -- sorted by (i, j); every
+        pair not listed has common 0.  `cap`: records to make room for at
+        first (default 8 per genome + 4096); when the rows hold more, the call
+        is repeated once with the size the library reports."""
+        N = len(nhash)
+        row1 = N if row1 is None else int(row1)
+        cap = int(cap) if cap is not None else 8 * N + 4096
+        buf = np.empty((max(cap, 1), 4), dtype=np.uint32)
+        rc, n = self.allpairs_sparse_raw(hashes, nhash, row0, row1, buf[:cap] if cap else None)
+        if rc == self.ERR_NOMEM:
+            buf = np.empty((n, 4), dtype=np.uint32)
+            rc, n = self.allpairs_sparse_raw(hashes, nhash, row0, row1, buf)
+            check(rc, "drephip_allpairs_sparse")
+        rec = buf[:n]
+        order = np.lexsort((rec[:, 1], rec[:, 0]))
+        rec = rec[order]
+        return (np.ascontiguousarray(rec[:, 0]), np.ascontiguousarray(rec[:, 1]),
+                rec[:, 2].astype(np.uint16), rec[:, 3].astype(np.uint16))
+
+    def allpairs_sparse_device(self, d_hashes: int, d_nhash: int, N: int, row0: int, row1: int,
+                               d_pairs: Optional[int], cap: int, stream: Optional[int] = None) -> Tuple[int, int]:
+        """drephip_allpairs_sparse_device: (return code, records the rows hold);
+        raises on every error but DREPHIP_ERR_NOMEM."""
+        n = C.c_uint64(0)
+        rc = lib().drephip_allpairs_sparse_device(self._h, d_hashes, d_nhash, N, row0, row1, d_pairs, cap,
+                                                  C.byref(n), stream)
+        if rc != self.ERR_NOMEM:
+            check(rc, "drephip_allpairs_sparse_device")
+        return rc, n.value
+
+    def sparse_stats(self) -> dict:
+        """{blocks, direct, fallback, scratch_bytes} of the last sparse all-pairs call."""
+        b, d, f, sb = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib().drephip_last_sparse_stats(self._h, C.byref(b), C.byref(d), C.byref(f), C.byref(sb)),
+              "drephip_last_sparse_stats")
+        return {"blocks": b.value, "direct": d.value, "fallback": f.value, "scratch_bytes": sb.value}
 
     def allpairs_device(self, d_hashes: int, d_nhash: int, N: int, row0: int, row1: int, d_common: int,
                         d_denom: Optional[int] = None, stream: Optional[int] = None, merge: bool = False):

@@ -27,6 +27,7 @@
 // Mash merge, one lane per pair; cross-check and fallback) are further down.
 
 #include "ctx.h"
+#include "sparse.h"
 #include "../../include/drephip.h"
 
 #include <algorithm>
@@ -58,7 +59,6 @@ constexpr uint32_t kFamTwins = 0x40;            // k_build_q32 family byte: the 
 constexpr uint32_t kFamFailed = 0xFF;           // ... no family worked (the row's pairs are merged literally)
 constexpr uint32_t kLdsBudget = 156 * 1024;     // dynamic LDS per workgroup
 constexpr uint32_t kScreenMinN = 4096;          // genomes from which the shared-hash screen runs (auto)
-constexpr uint32_t kListCols = 512;             // screened columns per whole-row LIST item
 
 __host__ __device__ __forceinline__ uint64_t cond_index(uint64_t i, uint64_t j, uint64_t N) {
     return i * N - i * (i + 1) / 2 + (j - i - 1);
@@ -479,8 +479,15 @@ __device__ __forceinline__ uint64_t ld_chunk_at(__amdgpu_buffer_rsrc_t rs, uint3
 // LIST (the screened path, screen.hip): the item's columns are clist[0..cend)
 // -- ascending, each sharing a hash with a row of the tile -- and c_first /
 // c_step walk that list instead of the column range.
+//
+// SPARSE (drephip_allpairs_sparse_device): nothing goes to the condensed
+// output.  A column's non-zero counts become records {i, c, common, denom}
+// staged one per lane in two registers of the wave (column; count,
+// denominator and row packed -- s <= 2048 on this path); when fewer than R
+// lanes are free, and after the item's last column, the wave reserves its
+// staged records' slots with one atomic add and stores them (sparse.h).
 template <int R, int NCH, bool FAST, int KB, bool MASKED, bool LIST = false, bool HITQ = false, bool HITV = false,
-          bool COLL = false>
+          bool COLL = false, bool SPARSE = false>
 __device__ __forceinline__ void ap_columns(const uint64_t *__restrict__ hashes, const uint32_t *__restrict__ nhash,
                                            const uint32_t *T, const uint32_t *V, uint32_t H, uint32_t hm, uint32_t s,
                                            uint32_t N, uint32_t i0, uint32_t nrows, uint32_t cend, uint32_t c_first,
@@ -490,8 +497,19 @@ __device__ __forceinline__ void ap_columns(const uint64_t *__restrict__ hashes, 
                                            const uint64_t (&thr1)[R], const uint64_t (&thr2)[R], uint32_t okmask,
                                            bool any_partial_row, uint16_t *__restrict__ common,
                                            uint16_t *__restrict__ denom, uint64_t seg0,
-                                           const uint32_t *__restrict__ cmask = nullptr) {
+                                           const uint32_t *__restrict__ cmask = nullptr, SparseOut sp = SparseOut{}) {
     const uint32_t lane = threadIdx.x & 63;
+    // SPARSE: the wave's staged records (lane k holds the k-th) and their count
+    uint32_t sp_col = 0, sp_val = 0, sp_n = 0;
+    auto sp_flush = [&]() {
+        if (sp_n == 0) return;                                        // wave-uniform
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(sp.count, (unsigned long long)sp_n);
+        const uint64_t b0 = ((uint64_t)rfl((uint32_t)(base >> 32)) << 32) | rfl((uint32_t)base);
+        if (lane < sp_n && b0 + lane < sp.cap)
+            sp.rec[b0 + lane] = make_uint4(i0 + (sp_val >> 24), sp_col, sp_val & 0xFFFu, (sp_val >> 12) & 0xFFFu);
+        sp_n = 0;
+    };
     const uint32_t lane_off = lane * 8u;
     const uint32_t nch = (s + 63) / 64;
     const uint32_t tail = s - (nch - 1) * 64;                        // valid lanes of the last chunk
@@ -716,7 +734,23 @@ __device__ __forceinline__ void ap_columns(const uint64_t *__restrict__ hashes, 
                 if (!group(kb, std::true_type{})) goto column_done;
         }
     column_done:
-        if (lane == 0) {
+        if constexpr (SPARSE) {
+            static_assert(R <= 8, "a record's row takes three bits");
+            const uint32_t nB = nhash[c];
+            const bool partial = any_partial_row || nB < s;
+            if (sp_n + R > 64) sp_flush();
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                if (!((actmask >> r) & 1u) || cnt[r] == 0) continue;     // wave-uniform
+                uint32_t dd = s;
+                if (partial) {
+                    const uint32_t u = nA[r] + nB - mrun_of(r);
+                    dd = u < s ? u : s;
+                }
+                if (lane == sp_n) { sp_col = c; sp_val = cnt[r] | (dd << 12) | ((uint32_t)r << 24); }
+                sp_n++;
+            }
+        } else if (lane == 0) {
             // the column's count is read only here: a scalar load left in flight
             // across the chunk loop would force every LDS wait there to lgkmcnt(0)
             const uint32_t nB = nhash[c];
@@ -738,6 +772,7 @@ __device__ __forceinline__ void ap_columns(const uint64_t *__restrict__ hashes, 
             }
         }
     }
+    if constexpr (SPARSE) sp_flush();
 }
 
 __host__ __device__ constexpr size_t q_lds_bytes(uint32_t R, uint32_t TS, uint32_t s) {
@@ -749,13 +784,15 @@ __host__ __device__ constexpr size_t q_lds_bytes(uint32_t R, uint32_t TS, uint32
 // (LDS <= 80 KiB, <= 64 VGPRs).
 // LIST: items are {i0, list offset, count, 0} over the screened column list
 // (screen.hip); otherwise {i0, c0, cend, 0} over the column range.
-template <int R, int NCH, int MINW, bool LIST = false>
+// SPARSE (with LIST): records of the non-zero pairs instead (ap_columns).
+template <int R, int NCH, int MINW, bool LIST = false, bool SPARSE = false>
 __global__ __launch_bounds__(kApWG, MINW) void k_allpairs_q(
     const uint64_t *__restrict__ hashes, const uint32_t *__restrict__ nhash,
     const uint32_t *__restrict__ blk, uint32_t stride, const uint8_t *__restrict__ fam, uint32_t s, uint32_t N,
     uint32_t row0, uint32_t row1, uint32_t B, const uint4 *__restrict__ items,
     uint16_t *__restrict__ common, uint16_t *__restrict__ denom, uint64_t seg0, const uint32_t *__restrict__ clist,
-    int hitq, const uint32_t *__restrict__ cmask) {
+    int hitq, const uint32_t *__restrict__ cmask, SparseOut sp) {
+    static_assert(LIST || !SPARSE, "the SPARSE flavour runs on the screened lists");
     constexpr int WG = kApWG;
     extern __shared__ __align__(16) uint32_t lds[];    // 16-B aligned: slot words are read with ds_read_b128
     const uint32_t H = 1u << B, hm = H - 1, TS = 2 * H;
@@ -841,21 +878,21 @@ __global__ __launch_bounds__(kApWG, MINW) void k_allpairs_q(
                                                                     thr2, ~failmask, any_partial_row, common, denom, seg0,
                                                                     cmask);
     else if (fast && !zero_key && hitq)
-        ap_columns<R, NCH, true, KB, false, LIST, true, true>(hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend,
-                                                        cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1, thr2,
-                                                        ~failmask, any_partial_row, common, denom, seg0);
+        ap_columns<R, NCH, true, KB, false, LIST, true, true, false, SPARSE>(
+            hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1, thr2,
+            ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
     else if (fast && !zero_key)
-        ap_columns<R, NCH, true, KB, false, LIST>(hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist,
-                                            nA, o1, o2, alast, thr1, thr2, ~failmask, any_partial_row, common, denom,
-                                            seg0);
+        ap_columns<R, NCH, true, KB, false, LIST, false, false, false, SPARSE>(
+            hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1, thr2,
+            ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
     else if (fast)
-        ap_columns<R, NCH, true, KB, true, LIST>(hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist,
-                                           nA, o1, o2, alast, thr1, thr2, ~failmask, any_partial_row, common, denom,
-                                           seg0);
+        ap_columns<R, NCH, true, KB, true, LIST, false, false, false, SPARSE>(
+            hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1, thr2,
+            ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
     else
-        ap_columns<R, NCH, false, KB, true, LIST>(hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist,
-                                            nA, o1, o2, alast, thr1, thr2, ~failmask, any_partial_row, common, denom,
-                                            seg0);
+        ap_columns<R, NCH, false, KB, true, LIST, false, false, false, SPARSE>(
+            hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1, thr2,
+            ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
     if (failmask) {
         // a row whose table could not be built (three of its keys share a low
         // word under every field family; never observed on real sketches):
@@ -866,9 +903,13 @@ __global__ __launch_bounds__(kApWG, MINW) void k_allpairs_q(
             if (!((failmask >> r) & 1u) || c <= i) continue;
             uint32_t cm, dd;
             merge_pair(hashes + (uint64_t)i * s, nhash[i], hashes + (uint64_t)c * s, nhash[c], s, cm, dd);
-            const uint64_t o = cond_index(i, c, N) - seg0;
-            common[o] = (uint16_t)cm;
-            if (denom) denom[o] = (uint16_t)dd;
+            if constexpr (SPARSE) {
+                if (cm) sparse_append(sp, i, c, cm, dd);
+            } else {
+                const uint64_t o = cond_index(i, c, N) - seg0;
+                common[o] = (uint16_t)cm;
+                if (denom) denom[o] = (uint16_t)dd;
+            }
         }
     }
 }
@@ -1590,13 +1631,13 @@ static int launch_band(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_
 }
 
 // LIST: the screened items / column list (clist)
-template <int R, int NCH, int MINW, bool LIST>
+template <int R, int NCH, int MINW, bool LIST, bool SPARSE = false>
 static int launch_q(drephip_ctx *ctx, uint32_t nitems, size_t lds, hipStream_t st, const uint64_t *h,
                     const uint32_t *nh, const uint32_t *blk, uint32_t stride, const uint8_t *fam, uint32_t N, uint32_t row0,
                     uint32_t row1, uint32_t B, const uint4 *items, uint16_t *cm, uint16_t *dn,
-                    uint64_t seg0, const uint32_t *clist, const uint32_t *cmask) {
-    HIPC(hipFuncSetAttribute((const void *)k_allpairs_q<R, NCH, MINW, LIST>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)lds));
+                    uint64_t seg0, const uint32_t *clist, const uint32_t *cmask, SparseOut sp = SparseOut{}) {
+    HIPC(hipFuncSetAttribute((const void *)k_allpairs_q<R, NCH, MINW, LIST, SPARSE>,
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // the branch-free hit probe and the union-rank end for rows with matches
     // (probe_rows_v, ap_columns HITQ/HITV); DREPHIP_AP_HIT=0 runs the round-5
     // probe and ends (A/B)
@@ -1604,10 +1645,10 @@ static int launch_q(drephip_ctx *ctx, uint32_t nitems, size_t lds, hipStream_t s
     const int hitq = he ? atoi(he) : 1;
     timing_mark(ctx, 2, st, true);
     for (uint32_t i0 = 0; i0 < nitems; i0 += (uint32_t)max_blocks(kApWG))
-        hipLaunchKernelGGL((k_allpairs_q<R, NCH, MINW, LIST>),
+        hipLaunchKernelGGL((k_allpairs_q<R, NCH, MINW, LIST, SPARSE>),
                            dim3(std::min<uint32_t>(nitems - i0, (uint32_t)max_blocks(kApWG))), dim3(kApWG), lds, st, h,
                            nh, blk, stride, fam, ctx->s, N, row0, row1, B, items + i0, cm, dn, seg0, clist, hitq,
-                           LIST ? nullptr : cmask);
+                           LIST ? nullptr : cmask, sp);
     timing_mark(ctx, 2, st, false);
     HIPC(hipGetLastError());
     return DREPHIP_OK;
@@ -1812,6 +1853,71 @@ int allpairs_device_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
     }
     HIPC(hipStreamSynchronize(st));
     return DREPHIP_OK;
+}
+
+// ------------------------------------------------------- sparse LIST launch
+// bytes of row-group image (slot words + high words) per row at R rows per tile
+uint64_t allpairs_image_bytes_per_row(drephip_ctx *ctx, uint32_t R) {
+    uint32_t B = 4;
+    while ((1u << B) < 2 * ctx->s) B++;
+    return (q_lds_bytes(R, 2u << B, ctx->s) + 15) / R;
+}
+
+// The screened items of rows [row0, row1) through the whole-row LIST kernel in
+// its SPARSE flavour: the row images are built as allpairs_device_impl builds
+// them, the kernel appends the non-zero pairs to `out`.  Queued on st.
+int allpairs_sparse_list_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
+                              uint32_t row0, uint32_t row1, uint32_t R, const ScreenResult &scr,
+                              const SparseOut &out, hipStream_t st) {
+    if (!scr.use || scr.nitems == 0) return DREPHIP_OK;
+    const uint32_t s = ctx->s;
+    uint32_t B = 4;
+    while ((1u << B) < 2 * s) B++;
+    const uint32_t TS = 2u << B;
+    const uint32_t ngroups = (row1 - row0 + R - 1) / R;
+    const uint32_t stride = (uint32_t)((q_lds_bytes(R, TS, s) / 4 + 3) & ~3ull);
+    uint32_t *d_blk;
+    uint8_t *d_fam;
+    int rc;
+    if ((rc = scratch(ctx, "ap_blk", (uint64_t)ngroups * stride * 4, (void **)&d_blk))) return rc;
+    if ((rc = scratch(ctx, "ap_fam", ((uint64_t)ngroups * R + 7) & ~7ull, (void **)&d_fam))) return rc;
+    const size_t blds = (size_t)TS * 4;
+    HIPC(hipFuncSetAttribute((const void *)k_build_q32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds));
+    timing_mark(ctx, 3, st, true);
+    hipLaunchKernelGGL(k_build_q32, dim3(ngroups * R), dim3(1024), blds, st, d_hashes, d_nhash, s, row0, row1, B, R,
+                       d_blk, stride, d_fam);
+    timing_mark(ctx, 3, st, false);
+    HIPC(hipGetLastError());
+    const size_t lds = (size_t)stride * 4;
+    const uint32_t nch = (s + 63) / 64;
+    const bool two = lds <= 80 * 1024;
+#define DREPHIP_QS1(RR, NC, MW) launch_q<RR, NC, MW, true, true>(ctx, scr.nitems, lds, st, d_hashes, d_nhash, d_blk, stride, d_fam, N, \
+                                                                 row0, row1, B, scr.items, nullptr, nullptr, 0, scr.clist, nullptr, out)
+#define DREPHIP_QS(RR, NC) (two ? DREPHIP_QS1(RR, NC, 8) : DREPHIP_QS1(RR, NC, 4))
+    if (nch <= 8) {
+        switch (R) {
+            case 8: rc = DREPHIP_QS(8, 8); break;
+            case 4: rc = DREPHIP_QS(4, 8); break;
+            case 2: rc = DREPHIP_QS(2, 8); break;
+            default: rc = DREPHIP_QS(1, 8); break;
+        }
+    } else if (nch <= 16) {
+        switch (R) {
+            case 8: rc = DREPHIP_QS(8, 16); break;
+            case 4: rc = DREPHIP_QS(4, 16); break;
+            case 2: rc = DREPHIP_QS(2, 16); break;
+            default: rc = DREPHIP_QS(1, 16); break;
+        }
+    } else {
+        switch (R) {
+            case 4: rc = DREPHIP_QS(4, 32); break;
+            case 2: rc = DREPHIP_QS(2, 32); break;
+            default: rc = DREPHIP_QS(1, 32); break;
+        }
+    }
+#undef DREPHIP_QS
+#undef DREPHIP_QS1
+    return rc;
 }
 
 // Completes a deferred table-path call (drephip_allpairs_device_async): waits

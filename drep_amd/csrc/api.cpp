@@ -134,7 +134,7 @@ static int refuse_if_pending(drephip_ctx *ctx) {
     return DREPHIP_ERR_ARG;
 }
 
-DREPHIP_EXPORT int drephip_version(void) { return 100; }
+DREPHIP_EXPORT int drephip_version(void) { return 200; }
 
 #ifndef DREPHIP_SRC_DIGEST
 #define DREPHIP_SRC_DIGEST "unknown"
@@ -875,6 +875,67 @@ DREPHIP_EXPORT int drephip_allpairs_rows(drephip_ctx *ctx, const uint64_t *hashe
                                          uint32_t row0, uint32_t row1, uint16_t *common_out, uint16_t *denom_out) {
     GUARD_CTX(ctx);
     return allpairs_host_rows(ctx, hashes, nhash, N, row0, row1, common_out, denom_out);
+}
+
+// ------------------------------------------------------------ sparse all-pairs
+DREPHIP_EXPORT int drephip_allpairs_sparse_device(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash,
+                                                  uint32_t N, uint32_t row0, uint32_t row1, uint32_t *d_pairs,
+                                                  uint64_t cap, uint64_t *n_pairs, void *stream) {
+    GUARD_CTX(ctx);
+    if (!d_hashes || !d_nhash || !n_pairs || (cap && !d_pairs)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    timing_begin(ctx);
+    int rc = allpairs_sparse_impl(ctx, d_hashes, d_nhash, N, row0, row1, (uint4 *)d_pairs, cap, n_pairs,
+                                  pick_stream(ctx, stream));
+    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
+    timing_collect(ctx);
+    return rc;
+}
+
+DREPHIP_EXPORT int drephip_allpairs_sparse(drephip_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash, uint32_t N,
+                                           uint32_t row0, uint32_t row1, uint32_t *pairs, uint64_t cap,
+                                           uint64_t *n_pairs) {
+    if (!ctx) { set_error("null context"); return DREPHIP_ERR_ARG; }
+    if (!hashes || !nhash || !n_pairs || (cap && !pairs)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    *n_pairs = 0;
+    const uint32_t s = ctx->s;
+    for (uint32_t i = 0; i < N; i++) {                    // the kernels read whole rows
+        if (nhash[i] > s) { set_error("nhash[i] > s"); return DREPHIP_ERR_ARG; }
+        const uint64_t *row = hashes + (uint64_t)i * s;
+        for (uint32_t j = 1; j < nhash[i]; j++)
+            if (row[j - 1] >= row[j]) { set_error("sketch rows must be ascending and distinct"); return DREPHIP_ERR_ARG; }
+        for (uint32_t j = nhash[i]; j < s; j++)
+            if (row[j] != ~0ull) { set_error("sketch rows must be UINT64_MAX past nhash[i]"); return DREPHIP_ERR_ARG; }
+    }
+    if (row1 > N) row1 = N;
+    if (N < 2 || row0 >= row1 || row0 >= N - 1) return DREPHIP_OK;
+    HIPC(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    uint64_t *d_h;
+    uint32_t *d_n, *d_p = nullptr;
+    int rc;
+    if ((rc = scratch(ctx, "ap_in_h", (uint64_t)N * s * 8, (void **)&d_h))) return rc;
+    if ((rc = scratch(ctx, "ap_in_n", N * 4ull, (void **)&d_n))) return rc;
+    if (cap && (rc = scratch(ctx, "sp_out", cap * 16, (void **)&d_p))) return rc;
+    HIPC(hipMemcpyAsync(d_h, hashes, (uint64_t)N * s * 8, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_n, nhash, N * 4ull, hipMemcpyHostToDevice, st));
+    timing_begin(ctx);
+    rc = allpairs_sparse_impl(ctx, d_h, d_n, N, row0, row1, (uint4 *)d_p, cap, n_pairs, st);
+    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
+    timing_collect(ctx);
+    const uint64_t have = std::min(*n_pairs, cap);
+    if (have) HIPC(hipMemcpyAsync(pairs, d_p, have * 16, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return rc;
+}
+
+DREPHIP_EXPORT int drephip_last_sparse_stats(drephip_ctx *ctx, uint32_t *blocks, uint64_t *direct, uint64_t *fallback,
+                                             uint64_t *scratch_bytes) {
+    if (!ctx) { set_error("null context"); return DREPHIP_ERR_ARG; }
+    if (blocks) *blocks = ctx->sparse.blocks;
+    if (direct) *direct = ctx->sparse.direct;
+    if (fallback) *fallback = ctx->sparse.fallback;
+    if (scratch_bytes) *scratch_bytes = ctx->sparse.scratch_bytes;
+    return DREPHIP_OK;
 }
 
 DREPHIP_EXPORT int drephip_distance_lut(int k, uint32_t denom, double *lut) {

@@ -117,6 +117,14 @@ struct ExtMarks {
     uint64_t nrec = 0;
 };
 
+// The last sparse all-pairs call (drephip_allpairs_sparse_device).
+struct SparseStats {
+    uint32_t blocks = 0;          // row blocks walked
+    uint64_t direct = 0;          // pairs appended by the screen and the LIST kernels themselves
+    uint64_t fallback = 0;        // pairs compacted out of a temporary condensed segment
+    uint64_t scratch_bytes = 0;   // context scratch after the call (grow-only: its peak)
+};
+
 // A run of all-pairs work items (allpairs.hip, plan_items): `size` row tiles
 // from i0 (step R) against column tile c0, at offset `off` of its XCD's list.
 struct ApItemGroup { uint32_t i0, c0, off, size; };
@@ -131,6 +139,7 @@ struct drephip_ctx {
     int ap_path = 0;          // DREPHIP_AP_*: 0 auto (table for s <= 2048, else band)
     int screen = 0;           // DREPHIP_SCREEN_*: 0 auto, 1 on, 2 off
     ScreenResult last_screen; // the last all-pairs call's screen (stats; pointers into scratch)
+    SparseStats sparse;       // the last sparse all-pairs call
     PartResult part;          // the last sharded-screen part (drephip_screen_part)
     ExtMarks ext;             // marks for the current drephip_allpairs_device_marked call
     int link_path = 0;        // DREPHIP_LINK_PATH_*: 0 auto (sparse when it applies, else dense)
@@ -259,6 +268,24 @@ bool screen_applies(drephip_ctx *ctx, uint32_t N);
 // min(s, |A| + |B|); the LIST kernels then overwrite the screened pairs.
 int screen_fill_impl(drephip_ctx *ctx, const uint32_t *d_nhash, uint32_t N, uint32_t row0, uint32_t row1,
                      uint64_t seg0, uint64_t npairs, uint16_t *d_common, uint16_t *d_denom, hipStream_t st);
+
+constexpr uint32_t kListCols = 512;             // screened columns per whole-row LIST item
+
+// The sparse all-pairs call (sparse.h; driver in screen.hip): rows [row0, row1)
+// as records {i, j, common, denom} of the pairs with common > 0 only, no
+// condensed vector.  *n_pairs = the records the rows hold (> cap: the list is
+// incomplete, nothing is stored past cap).  Blocking.
+struct SparseOut;
+int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
+                         uint32_t row0, uint32_t row1, uint4 *d_pairs, uint64_t cap, uint64_t *n_pairs,
+                         hipStream_t st);
+// allpairs.hip: the whole-row LIST kernel in its SPARSE flavour over the
+// screened items of rows [row0, row1) (tables built here; queued, no sync), and
+// the bytes of table image a row takes
+int allpairs_sparse_list_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
+                              uint32_t row0, uint32_t row1, uint32_t R, const ScreenResult &scr,
+                              const SparseOut &out, hipStream_t st);
+uint64_t allpairs_image_bytes_per_row(drephip_ctx *ctx, uint32_t R);
 
 // Primary clustering (linkage.hip).
 int linkage_device_impl(drephip_ctx *ctx, double *d_D, uint32_t n, int method, double *Z_out, hipStream_t st);

@@ -36,6 +36,7 @@
 // the dense kernels' O(N^2 s).
 
 #include "ctx.h"
+#include "sparse.h"
 #include "../../include/drephip.h"
 
 #include <hipcub/device/device_radix_sort.hpp>
@@ -541,6 +542,16 @@ __global__ __launch_bounds__(kScWG) void k_cells_scatter(const uint4 *__restrict
 // right).  Pairs held by several runs, or with a partial sketch (whose
 // denominator depends on the merge), mark their cell for the LIST kernel,
 // which runs after this and rewrites every pair of a marked cell exactly.
+//
+// SPARSE (the sparse all-pairs call, sparse.h): a pair must have exactly one
+// writer, so the kernel runs twice.  Phase 0 only marks (the pairs held by
+// several runs, or with a partial sketch); phase 1, with every mark of the
+// block in place, appends {a, b, 1, s} for the pairs of unmarked cells whose
+// rank sum is below s and nothing for the others -- a pair whose cell another
+// pair marked belongs to the LIST kernel alone.  (In the dense form a cell
+// marked after its pair was written is harmless: the kernel stores the same
+// count again.)
+template <bool SPARSE>
 __global__ __launch_bounds__(kScWG) void k_screen_simple(const unsigned long long *__restrict__ pkey,
                                                          const uint32_t *__restrict__ pcnt,
                                                          const uint32_t *__restrict__ ppos, uint32_t pcap,
@@ -548,7 +559,8 @@ __global__ __launch_bounds__(kScWG) void k_screen_simple(const unsigned long lon
                                                          uint32_t row0, uint32_t rshift, uint32_t NW,
                                                          uint64_t seg0, uint32_t *__restrict__ bm,
                                                          uint32_t *__restrict__ bmH,
-                                                         uint16_t *__restrict__ common, unsigned long long *__restrict__ nsimple) {
+                                                         uint16_t *__restrict__ common, unsigned long long *__restrict__ nsimple,
+                                                         SparseOut sp, int phase) {
     uint32_t mine = 0;
     for (uint32_t q = blockIdx.x * kScWG + threadIdx.x; q < pcap; q += gridDim.x * kScWG) {
         const unsigned long long key = pkey[q];
@@ -557,6 +569,25 @@ __global__ __launch_bounds__(kScWG) void k_screen_simple(const unsigned long lon
         const uint64_t wo = (uint64_t)((a - row0) >> rshift) * NW + (b >> 5);
         uint32_t *w = bm + wo;
         const uint32_t bit = 1u << (b & 31);
+        if constexpr (SPARSE) {
+            const bool kernel_pair = pcnt[q] >= 2 || nh[a] != s || nh[b] != s;
+            if (phase == 0) {
+                // (bmH: with light cells, also a pair whose cell a longer run marked --
+                // the pair shares a second hash, the cell is the LIST kernel's)
+                if (kernel_pair) {
+                    atomicOr(w, bit);
+                    if (bmH) atomicOr(bmH + wo, bit);
+                } else if (bmH && (*w & bit)) {
+                    atomicOr(bmH + wo, bit);
+                }
+                continue;
+            }
+            if (kernel_pair || (*w & bit)) continue;
+            const uint32_t pos = ppos[q];
+            if (((pos >> 16) + (pos & 0xFFFFu)) < s) sparse_append(sp, a, b, 1u, s);
+            mine++;
+            continue;
+        }
         // (bmH, the light screen's heavy cells: the cell needs the LIST kernel)
         if (pcnt[q] >= 2 || nh[a] != s || nh[b] != s) {
             atomicOr(w, bit);
@@ -780,6 +811,11 @@ __global__ __launch_bounds__(kMarkWG) void k_screen_mark(const uint32_t *__restr
 // configs[4] these are most cells: unrelated families sharing one hash by
 // chance (each such hash marks family x family cells).  A cell with a partial
 // sketch goes heavy.  One thread per bitmap word.
+// SPARSE (sparse.h): a cell is either light or heavy as a whole before any of
+// its pairs is appended -- the rows are searched once for a row holding two
+// entries of the run (heavy: the LIST kernel appends the cell's pairs), then
+// again to append {r, c, 1, s} where the rank sum is below s.
+template <bool SPARSE>
 __global__ __launch_bounds__(kScWG) void k_screen_light(const uint32_t *__restrict__ bm, uint32_t *__restrict__ bmH,
                                                         const uint32_t *__restrict__ crun, const uint2 *__restrict__ runs,
                                                         const uint32_t *__restrict__ vals, const uint64_t *__restrict__ H,
@@ -787,7 +823,7 @@ __global__ __launch_bounds__(kScWG) void k_screen_light(const uint32_t *__restri
                                                         uint32_t N, uint32_t row0, uint32_t row1, uint32_t R,
                                                         uint32_t NW, uint64_t nwords, uint64_t seg0,
                                                         uint16_t *__restrict__ common,
-                                                        unsigned long long *__restrict__ nlight) {
+                                                        unsigned long long *__restrict__ nlight, SparseOut sp) {
     uint32_t mine = 0;
     for (uint64_t wi = (uint64_t)blockIdx.x * kScWG + threadIdx.x; wi < nwords; wi += (uint64_t)gridDim.x * kScWG) {
         uint32_t L = bm[wi] & ~bmH[wi];
@@ -831,6 +867,25 @@ __global__ __launch_bounds__(kScWG) void k_screen_light(const uint32_t *__restri
             // be a second run marking the cell -- unless it holds two of them
             const uint64_t hc = H[(uint64_t)c * s + pc];
             uint32_t wrote = 0;
+            if constexpr (SPARSE) {
+                bool two = false;
+                for (uint32_t j = 0; j < R && !two; j++) {
+                    const uint32_t r = r0 + j;
+                    if (r >= row1 || r >= c) break;
+                    two = find(r, dup) >= 0 && dup;
+                }
+                if (two) { heavy |= 1u << b; continue; }
+                for (uint32_t j = 0; j < R; j++) {
+                    const uint32_t r = r0 + j;
+                    if (r >= row1 || r >= c) break;
+                    const int32_t pr = find(r, dup);
+                    if (pr < 0 || H[(uint64_t)r * s + pr] != hc) continue;
+                    if ((uint32_t)(pr + pc) < s) sparse_append(sp, r, c, 1u, s);
+                    wrote++;
+                }
+                mine += wrote;
+                continue;
+            }
             for (uint32_t j = 0; j < R; j++) {
                 const uint32_t r = r0 + j;
                 if (r >= row1 || r >= c) break;
@@ -1315,15 +1370,15 @@ int screen_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nh
         hipLaunchKernelGGL(k_screen_mark2, dim3(g2), dim3(kScWG), 0, st, F.v_out, d_hashes, s, F.vmask, F.pairs, F.n2, row0, row1,
                            pkey, pcnt, ppos, (uint32_t)(pcap - 1));
         const uint32_t gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (pcap + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_simple, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N, row0,
-                           rshift, NW, seg0, d_bm, d_bmH, d_common, d_nsimple);
+        hipLaunchKernelGGL(k_screen_simple<false>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
+                           row0, rshift, NW, seg0, d_bm, d_bmH, d_common, d_nsimple, SparseOut{}, 0);
     }
     prof.mark("mark", st);
     if (light && F.nruns) {
         const uint64_t nwords = (uint64_t)ntiles * NW;
         const uint32_t gl = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, (nwords + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_light, dim3(gl), dim3(kScWG), 0, st, d_bm, d_bmH, d_crun, F.runs, F.v_out, d_hashes,
-                           d_nhash, s, F.vmask, N, row0, row1, R, NW, nwords, seg0, d_common, d_nsimple);
+        hipLaunchKernelGGL(k_screen_light<false>, dim3(gl), dim3(kScWG), 0, st, d_bm, d_bmH, d_crun, F.runs, F.v_out, d_hashes,
+                           d_nhash, s, F.vmask, N, row0, row1, R, NW, nwords, seg0, d_common, d_nsimple, SparseOut{});
         prof.mark("light", st);
     }
     // the LIST kernels take the heavy cells (every marked cell without the light screen)
@@ -1461,8 +1516,8 @@ int screen_marked_impl(drephip_ctx *ctx, const uint32_t *d_nhash, uint32_t N, ui
         hipLaunchKernelGGL(k_screen_map2, dim3(g2), dim3(kScWG), 0, st, d_rec, nrec, row0, row1, pkey, pcnt, ppos,
                            (uint32_t)(pcap - 1));
         const uint32_t gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (pcap + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_simple, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
-                           row0, rshift, NW, seg0, d_bm, nullptr, d_common, d_nsimple);
+        hipLaunchKernelGGL(k_screen_simple<false>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
+                           row0, rshift, NW, seg0, d_bm, nullptr, d_common, d_nsimple, SparseOut{}, 0);
     }
     prof.mark("pairs", st);
     HIPC(hipGetLastError());
@@ -1484,6 +1539,260 @@ int screen_fill_impl(drephip_ctx *ctx, const uint32_t *d_nhash, uint32_t N, uint
         hipLaunchKernelGGL(k_screen_denoms, dim3(row1 - row0), dim3(kScWG), 0, st, d_nhash, ctx->s, N, row0, seg0,
                            d_denom);
     HIPC(hipGetLastError());
+    return DREPHIP_OK;
+}
+
+// ------------------------------------------------------ the sparse all-pairs
+// drephip_allpairs_sparse_device: rows [row0, row1) as a list of the pairs
+// that share a hash, {i, j, common, denom}, without the condensed vector.
+//
+// Direct path (whole-row tables, the screen applies and does not give the
+// dense verdict): the entries are grouped once per call (screen_front); the
+// rows are then walked in blocks of a multiple of R rows, so that the
+// row-proportional scratch -- the cell bitmap, ntiles x N / 32 words, and the
+// row images -- stays inside a budget.  Per block the marking runs as in
+// screen_impl, without the no-shared-hash fill and without light cells, and
+// every pair has one writer: k_screen_simple<true> for a pair held by one run
+// of two in an unmarked cell, the SPARSE LIST kernel for every pair of a
+// marked cell.
+//
+// Fallback (every other plan: band path, screen off or dense verdict, N x s >=
+// 2^32, the literal merge; and the rest of a call once a block's pair map or
+// lists outgrow the screen's limits): allpairs_device_impl into a temporary
+// condensed segment of the context, at most kSegPairs pairs per array, whose
+// non-zero counts are compacted into the list in two passes -- a count per
+// row, a scan, then each row's records written in order at its offset.
+constexpr uint64_t kSegPairs = 1ull << 28;
+
+// non-zero counts of each row of the segment (one workgroup per row)
+__global__ __launch_bounds__(kScWG) void k_sp_count(const uint16_t *__restrict__ common, uint32_t N, uint32_t row0,
+                                                    uint64_t seg0, uint64_t *__restrict__ cnt) {
+    __shared__ uint32_t red[kScWG / 64];
+    const uint32_t i = row0 + blockIdx.x;
+    const uint16_t *row = common + ((uint64_t)i * N - (uint64_t)i * (i + 1) / 2 - seg0);
+    const uint32_t len = N - 1 - i;
+    uint32_t c = 0;
+    for (uint32_t t = threadIdx.x; t < len; t += kScWG) c += row[t] != 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < kScWG / 64; w++) t += red[w];
+        cnt[blockIdx.x] = t;
+    }
+}
+// each row's records {i, j, common, denom} in column order at base + off[row];
+// nothing is stored at or past cap
+__global__ __launch_bounds__(kScWG) void k_sp_write(const uint16_t *__restrict__ common,
+                                                    const uint16_t *__restrict__ denom, uint32_t N, uint32_t row0,
+                                                    uint64_t seg0, const uint64_t *__restrict__ off, uint64_t base,
+                                                    uint4 *__restrict__ rec, uint64_t cap) {
+    __shared__ uint32_t wsum[kScWG / 64];
+    const uint32_t i = row0 + blockIdx.x;
+    const uint64_t ro = (uint64_t)i * N - (uint64_t)i * (i + 1) / 2 - seg0;
+    const uint32_t len = N - 1 - i;
+    uint64_t o = base + off[blockIdx.x];
+    for (uint32_t tb = 0; tb < len; tb += kScWG) {                    // uniform trip count
+        const uint32_t t = tb + threadIdx.x;
+        const uint32_t c = t < len ? common[ro + t] : 0u;
+        uint32_t tot;
+        const uint64_t q = o + block_exclusive_count(c != 0, wsum, &tot);
+        if (c && q < cap) rec[q] = make_uint4(i, i + 1 + t, c, denom[ro + t]);
+        o += tot;
+    }
+}
+
+// one block of the direct path: marks, lists and the pairs the screen writes
+// itself; res->use = false (nothing appended) when the block outgrows the
+// screen's limits
+static int sparse_direct_block(drephip_ctx *ctx, const ScreenFront &F, const uint64_t *d_hashes,
+                               const uint32_t *d_nhash, uint32_t N, uint32_t row0, uint32_t row1, uint32_t R,
+                               const SparseOut &out, hipStream_t st, ScreenProf &prof, ScreenResult *res,
+                               unsigned long long **d_nsimple_out) {
+    *res = ScreenResult{};
+    *d_nsimple_out = nullptr;
+    res->entries = F.M;
+    if (F.M < 2) {                                   // no two entries: no pair shares a hash
+        res->use = true;
+        return DREPHIP_OK;
+    }
+    res->runs = (uint64_t)F.n2 + F.nruns;
+    res->checks = F.E;
+    const uint32_t s = ctx->s;
+    const uint32_t ntiles = (row1 - row0 + R - 1) / R, NW = (N + 31) / 32, rshift = tile_shift(R);
+    int rc;
+    uint32_t *d_bm;
+    if ((rc = scratch(ctx, "sc_bitmap", (uint64_t)ntiles * NW * 4, (void **)&d_bm))) return rc;
+    uint64_t pcap;
+    unsigned long long *pkey = nullptr, *d_nsimple;
+    uint32_t *pcnt = nullptr, *ppos = nullptr;
+    if ((rc = screen_pair_map(ctx, F.n2, st, &pcap, &pkey, &pcnt, &ppos))) return rc;
+    if (pcap > kMaxPairMap) return DREPHIP_OK;
+    if ((rc = scratch(ctx, "sc_nsimple", 8, (void **)&d_nsimple))) return rc;
+    // light cells (k_screen_light): off on this path unless DREPHIP_SCREEN_LIGHT=1
+    // asks for them (screen_impl takes them by default with the band kernel only)
+    const char *le = getenv("DREPHIP_SCREEN_LIGHT");
+    const bool light = le && atoi(le) != 0 && F.nruns && (uint64_t)ntiles * N * 4 <= kLightBudget;
+    uint32_t *d_bmH = nullptr, *d_crun = nullptr;
+    if (light) {
+        if ((rc = scratch(ctx, "sc_bitmap_heavy", (uint64_t)ntiles * NW * 4, (void **)&d_bmH))) return rc;
+        if ((rc = scratch(ctx, "sc_crun", (uint64_t)ntiles * N * 4, (void **)&d_crun))) return rc;
+        HIPC(hipMemsetAsync(d_bmH, 0, (uint64_t)ntiles * NW * 4, st));
+    }
+    HIPC(hipMemsetAsync(d_bm, 0, (uint64_t)ntiles * NW * 4, st));
+    HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
+    if ((rc = screen_mark_runs(ctx, F, d_hashes, N, row0, row1, rshift, NW, d_bm, d_bmH, d_crun, st, prof))) return rc;
+    const uint32_t gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (pcap + kScWG - 1) / kScWG));
+    if (F.n2) {
+        const uint32_t g2 = std::max(1u, std::min(8192u, (F.n2 + kScWG - 1) / kScWG));
+        hipLaunchKernelGGL(k_screen_mark2, dim3(g2), dim3(kScWG), 0, st, F.v_out, d_hashes, s, F.vmask, F.pairs, F.n2, row0, row1,
+                           pkey, pcnt, ppos, (uint32_t)(pcap - 1));
+        hipLaunchKernelGGL(k_screen_simple<true>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
+                           row0, rshift, NW, 0ull, d_bm, d_bmH, nullptr, d_nsimple, out, 0);
+    }
+    prof.mark("mark", st);
+    // the cells left to the LIST kernel: all marked ones, or (light) the heavy
+    // ones -- final only after k_screen_light, which therefore runs before the
+    // lists and appends; a block that then does not fit the lists' limits
+    // cannot be handed to the fallback any more
+    if (light) {
+        const uint64_t nwords = (uint64_t)ntiles * NW;
+        const uint32_t gl = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, (nwords + kScWG - 1) / kScWG));
+        hipLaunchKernelGGL(k_screen_light<true>, dim3(gl), dim3(kScWG), 0, st, d_bm, d_bmH, d_crun, F.runs, F.v_out, d_hashes,
+                           d_nhash, s, F.vmask, N, row0, row1, R, NW, nwords, 0ull, nullptr, d_nsimple, out);
+        prof.mark("light", st);
+    }
+    if ((rc = screen_lists(ctx, light ? d_bmH : d_bm, ntiles, NW, kListCols, row0, R, d_nsimple, st, prof, res))) return rc;
+    if (!res->use) {
+        if (light) { set_error("sparse all-pairs: the light screen's block outgrew the list limits"); return DREPHIP_ERR_INTERNAL; }
+        return DREPHIP_OK;
+    }
+    // every mark is in place (and the block is known to fit): the pairs of one run of two
+    if (F.n2)
+        hipLaunchKernelGGL(k_screen_simple<true>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
+                           row0, rshift, NW, 0ull, d_bm, d_bmH, nullptr, d_nsimple, out, 1);
+    HIPC(hipGetLastError());
+    *d_nsimple_out = d_nsimple;
+    return DREPHIP_OK;
+}
+
+int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
+                         uint32_t row0, uint32_t row1, uint4 *d_pairs, uint64_t cap, uint64_t *n_pairs,
+                         hipStream_t st) {
+    *n_pairs = 0;
+    ctx->sparse = SparseStats{};
+    if (ctx->apend.active) {
+        int rc = allpairs_wait_impl(ctx);
+        if (rc) return rc;
+    }
+    ctx->last_screen = ScreenResult{};
+    if (row1 > N) row1 = N;
+    if (N < 2 || row0 >= row1 || row0 >= N - 1) return DREPHIP_OK;
+    if (row1 > N - 1) row1 = N - 1;                   // the last genome has no pair of its own
+    const uint32_t s = ctx->s;
+    uint32_t R = 1;
+    int path = DREPHIP_AP_MERGE, rc;
+    if ((rc = allpairs_geometry(ctx, &R, &path))) return rc;
+    uint64_t env_rows = 0;
+    if (const char *e = getenv("DREPHIP_SPARSE_BLOCK_ROWS")) env_rows = strtoull(e, nullptr, 10);
+    unsigned long long *d_count;
+    uint64_t *h_tot;
+    if ((rc = scratch(ctx, "sp_count", 8, (void **)&d_count))) return rc;
+    if ((rc = pinned_host(ctx, "sp_tot", 64, (void **)&h_tot))) return rc;
+    uint64_t total = 0;
+    uint32_t b0 = row0;
+
+    bool direct = path == DREPHIP_AP_TABLE && !ctx->ext.active && screen_applies(ctx, N);
+    ScreenProf prof;
+    ScreenFront F;
+    if (direct) {
+        prof.mark("start", st);
+        timing_mark(ctx, 4, st, true);
+        rc = screen_front(ctx, d_hashes, d_nhash, N, 0, 1, st, prof, &F);
+        timing_mark(ctx, 4, st, false);
+        if (rc) return rc;
+        // the dense verdict (auto mode): the fallback runs the dense item plan
+        if (F.M >= 2 && screen_mode(ctx) != DREPHIP_SCREEN_ON && !screen_worth(N, s, F.E)) direct = false;
+    }
+    if (direct) {
+        const uint32_t NW = (N + 31) / 32;
+        uint64_t rows = env_rows;
+        if (!rows) {
+            // an eighth of the free HBM each for the two buffers that grow
+            // with the block's rows: the cell bitmap and the row images
+            size_t fr = 0, tot = 0;
+            HIPC(hipMemGetInfo(&fr, &tot));
+            const uint64_t budget = std::max<uint64_t>(fr / 8, 1ull << 20);
+            rows = std::min(budget * R / ((uint64_t)NW * 4), budget / allpairs_image_bytes_per_row(ctx, R));
+        }
+        rows = std::max<uint64_t>(R, (rows + R - 1) / R * R);
+        HIPC(hipMemsetAsync(d_count, 0, 8, st));
+        const SparseOut out{d_pairs, d_count, cap};
+        ScreenResult acc;
+        while (b0 < row1) {
+            const uint32_t b1 = (uint32_t)std::min<uint64_t>(row1, (uint64_t)b0 + rows);
+            ScreenResult res;
+            unsigned long long *d_nsimple = nullptr;
+            timing_mark(ctx, 4, st, true);
+            rc = sparse_direct_block(ctx, F, d_hashes, d_nhash, N, b0, b1, R, out, st, prof, &res, &d_nsimple);
+            timing_mark(ctx, 4, st, false);
+            if (rc) return rc;
+            if (!res.use) break;                      // this block and the rest: the fallback
+            if ((rc = allpairs_sparse_list_impl(ctx, d_hashes, d_nhash, N, b0, b1, R, res, out, st))) return rc;
+            HIPC(hipMemcpyAsync(h_tot, d_count, 8, hipMemcpyDeviceToHost, st));
+            if (d_nsimple) HIPC(hipMemcpyAsync(h_tot + 1, d_nsimple, 8, hipMemcpyDeviceToHost, st));
+            HIPC(hipStreamSynchronize(st));
+            total = h_tot[0];
+            acc.use = true;
+            acc.entries = res.entries;
+            acc.runs = res.runs;
+            acc.checks = res.checks;
+            acc.marked += res.marked;
+            acc.simple += d_nsimple ? h_tot[1] : 0;
+            ctx->sparse.blocks++;
+            b0 = b1;
+        }
+        ctx->sparse.direct = total;
+        ctx->last_screen = acc;                       // (stats only: no list pointers)
+    }
+
+    while (b0 < row1) {
+        // rows of at most kSegPairs pairs (at least one row)
+        uint32_t b1 = b0;
+        uint64_t np = 0;
+        while (b1 < row1 && (b1 == b0 || (env_rows ? b1 - b0 < env_rows : np + (N - 1 - b1) <= kSegPairs))) {
+            np += N - 1 - b1;
+            b1++;
+        }
+        const uint32_t nrows = b1 - b0;
+        uint16_t *d_c, *d_d;
+        uint64_t *d_cnt, *d_off;
+        if ((rc = scratch(ctx, "sp_seg_common", np * 2, (void **)&d_c))) return rc;
+        if ((rc = scratch(ctx, "sp_seg_denom", np * 2, (void **)&d_d))) return rc;
+        if ((rc = scratch(ctx, "sp_row_cnt", (nrows + 1) * 8ull, (void **)&d_cnt))) return rc;
+        if ((rc = scratch(ctx, "sp_row_off", (nrows + 1) * 8ull, (void **)&d_off))) return rc;
+        if ((rc = allpairs_device_impl(ctx, d_hashes, d_nhash, N, b0, b1, d_c, d_d, st, false))) return rc;
+        const uint64_t seg0 = (uint64_t)b0 * N - (uint64_t)b0 * (b0 + 1) / 2;
+        HIPC(hipMemsetAsync(d_cnt + nrows, 0, 8, st));
+        hipLaunchKernelGGL(k_sp_count, dim3(nrows), dim3(kScWG), 0, st, d_c, N, b0, seg0, d_cnt);
+        if ((rc = hip_scan(ctx, "sp_scan_tmp", d_cnt, d_off, nrows + 1, st))) return rc;
+        hipLaunchKernelGGL(k_sp_write, dim3(nrows), dim3(kScWG), 0, st, d_c, d_d, N, b0, seg0, d_off, total, d_pairs, cap);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(h_tot, d_off + nrows, 8, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        total += h_tot[0];
+        ctx->sparse.fallback += h_tot[0];
+        ctx->sparse.blocks++;
+        b0 = b1;
+    }
+    for (const auto &kv : ctx->bufs) ctx->sparse.scratch_bytes += kv.second.bytes;
+    *n_pairs = total;
+    if (total > cap) {
+        set_error("the pair list holds " + std::to_string(total) + " records, the buffer " + std::to_string(cap));
+        return DREPHIP_ERR_NOMEM;
+    }
     return DREPHIP_OK;
 }
 

@@ -693,3 +693,125 @@ def cluster_mash_condensed(cm: CondensedMash, **kwargs):
     arguments = {'linkage_method': P_Lmethod, 'linkage_cutoff': P_Lcutoff,
                  'comparison_algorithm': 'MASH'}
     return Cdb, [linkage, None, arguments]
+
+
+# ------------------------------------------------------- the sparse pipeline
+# Beyond ~2x10^5 genomes the condensed triangle itself no longer fits (1 TB per
+# array at 10^6): the all-pairs step then lists only the pairs that share a
+# hash (libdrephip drephip_allpairs_sparse), and everything downstream works on
+# that list -- a pair that is not listed has common 0, Mash distance 1.
+@dataclass
+class SparseMash:
+    names: List[str]
+    locations: List[str]
+    i: np.ndarray          # uint32, i < j, sorted by (i, j)
+    j: np.ndarray          # uint32
+    common: np.ndarray     # uint16, > 0
+    denom: np.ndarray      # uint16
+    nhash: np.ndarray
+    length: np.ndarray
+    s: int
+
+
+def sparse_allpairs(hashes: np.ndarray, nhash: np.ndarray, s: int, devices: Sequence[int] = (0,)):
+    """(i, j, common, denom) of the pairs sharing a hash, sorted by (i, j).
+    With several devices the rows are split as condensed_allpairs splits them
+    (parallel.row_partition), one context and host thread per device; a row
+    range's list holds the pairs whose smaller genome is one of its rows, so
+    the ranges' lists are concatenated in order."""
+    N = len(nhash)
+    parts = row_partition(N, len(devices))
+
+    def run(k, dev):
+        r0, r1 = parts[k]
+        if r1 <= r0:
+            return tuple(np.zeros(0, t) for t in (np.uint32, np.uint32, np.uint16, np.uint16))
+        with _lib.Context(device=dev, k=MASH_K, s=s, seed=MASH_SEED) as ctx:
+            return ctx.allpairs_sparse(hashes, nhash, r0, r1)
+    res = _on_devices(list(devices), run) if N >= 2 else []
+    if not res:
+        return tuple(np.zeros(0, t) for t in (np.uint32, np.uint32, np.uint16, np.uint16))
+    return tuple(np.concatenate([r[k] for r in res]) for k in range(4))
+
+
+def all_vs_all_MASH_sparse(Bdb, data_folder, **kwargs) -> SparseMash:
+    """Sketch (or load cached sketches) and run the sparse HIP all-pairs: the
+    pairs that share a hash instead of the condensed triangle (reference
+    drep/d_cluster.py:481-596 keeps every pair as a row of MASH_table.tsv).
+    Same keyword arguments as all_vs_all_MASH_condensed."""
+    sk = sketch_genomes(Bdb, data_folder, **kwargs)
+    with _Stage('allpairs_s'):
+        i, j, common, denom = sparse_allpairs(sk.hashes, sk.nhash, sk.s, _devices(kwargs))
+    return SparseMash(sk.names, sk.locations, i, j, common, denom, sk.nhash, sk.length, sk.s)
+
+
+def _sparse_pairs(sm: SparseMash):
+    """The listed pairs plus the pairs of two empty sketches: Mash gives those
+    common = denom = 0 and distance 0 (mash_distance_float32), below 1 like
+    the listed ones although they share no hash."""
+    i, j = np.asarray(sm.i, dtype=np.uint32), np.asarray(sm.j, dtype=np.uint32)
+    c, d = np.asarray(sm.common, dtype=np.uint16), np.asarray(sm.denom, dtype=np.uint16)
+    empty = np.nonzero(np.asarray(sm.nhash) == 0)[0].astype(np.uint32)
+    if len(empty) >= 2:
+        a, b = np.triu_indices(len(empty), 1)
+        i, j = np.concatenate([i, empty[a]]), np.concatenate([j, empty[b]])
+        c = np.concatenate([c, np.zeros(len(a), np.uint16)])
+        d = np.concatenate([d, np.zeros(len(a), np.uint16)])
+    return i, j, c, d
+
+
+def cluster_mash_sparse(sm: SparseMash, **kwargs):
+    """cluster_mash_condensed from the pair list: the same Cdb and the same
+    linkage Z, bit for bit (reference cluster_mash_database,
+    drep/d_cluster.py:598-630).  The linkage input holds the listed pairs'
+    values (_linkage_values) at the rows linkage_order gives the genomes and
+    1.0 everywhere else, which is what libdrephip's sparse linkage
+    (drephip_linkage_sparse: scipy's algorithm over the pairs below 1.0, on
+    the host) takes."""
+    P_Lmethod = kwargs.get('clusterAlg', 'single')
+    P_Lcutoff = 1 - kwargs.get('P_ani', .9)
+    if P_Lmethod not in GPU_LINKAGE_METHODS:
+        raise ValueError("cluster_mash_sparse supports clusterAlg in %s" % (GPU_LINKAGE_METHODS,))
+    names = sorted(sm.names)
+    N = len(sm.names)
+    i, j, c, d = _sparse_pairs(sm)
+    vals = _linkage_values(c, d)
+    perm = linkage_order(sm.names)
+    keep = vals < 1.0
+    linkage = _lib.linkage_sparse(N, perm[i[keep]], perm[j[keep]], vals[keep], P_Lmethod)
+    fclust = scipy.cluster.hierarchy.fcluster(linkage, P_Lcutoff, criterion='distance') if N >= 2 \
+        else np.ones(N, dtype=np.int32)
+    Cdb = _primary_cdb(fclust, names)
+    arguments = {'linkage_method': P_Lmethod, 'linkage_cutoff': P_Lcutoff,
+                 'comparison_algorithm': 'MASH'}
+    return Cdb, [linkage, None, arguments]
+
+
+def mdb_from_sparse(sm: SparseMash, k: int = MASH_K) -> pd.DataFrame:
+    """The rows of the Mdb all_vs_all_MASH returns (drep/d_cluster.py:575-596)
+    whose dist is below 1, the diagonal included: same row order (and index:
+    row t = q N + r of the full table is genome1 = genome r, genome2 = genome
+    q), dtypes, ordered categories and float32 dist / similarity bits as
+    mdb_from_condensed(...)[dist < 1], built from the same float32 tables."""
+    N = len(sm.names)
+    i, j, c, d = _sparse_pairs(sm)
+    dens = np.unique(d) if len(d) else np.array([sm.s])
+    lut32, lut_off = float32_tables(dens, sm.s, k)
+    dp = lut32[lut_off[d.astype(np.int64)].astype(np.int64) + c.astype(np.int64)] if len(d) \
+        else np.zeros(0, np.float32)
+    diag = np.arange(N, dtype=np.int64)
+    r = np.concatenate([i.astype(np.int64), j.astype(np.int64), diag])
+    q = np.concatenate([j.astype(np.int64), i.astype(np.int64), diag])
+    dist = np.concatenate([dp, dp, np.zeros(N, np.float32)]).astype(np.float32)
+    t = q * N + r
+    order = np.argsort(t, kind='stable')
+    order = order[dist[order] < 1]
+    dist = dist[order]
+    cats = sorted(set(sm.names))
+    dtype = pd.CategoricalDtype(cats, ordered=True)
+    code_t = pd.Categorical([], dtype=dtype).codes.dtype
+    pos = {n: x for x, n in enumerate(cats)}
+    codes = np.array([pos[n] for n in sm.names], dtype=code_t)
+    return pd.DataFrame({'genome1': pd.Categorical.from_codes(codes[r[order]], dtype=dtype, validate=False),
+                         'genome2': pd.Categorical.from_codes(codes[q[order]], dtype=dtype, validate=False),
+                         'dist': dist, 'similarity': np.float32(1) - dist}, index=t[order], copy=False)

@@ -37,9 +37,10 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .d_cluster import MASH_K, MASH_SEED, CondensedMash
+from .d_cluster import MASH_K, MASH_SEED, CondensedMash, SparseMash
 
 CONDENSED_SUBDIR = os.path.join("MASH_files", "condensed")
+SPARSE_SUBDIR = os.path.join("MASH_files", "sparse")
 PRIMARY_LINKAGE = os.path.join("Clustering_files", "primary_linkage.pickle")
 
 
@@ -96,6 +97,57 @@ def load_condensed(data_folder: str, mmap: bool = True) -> CondensedMash:
     return CondensedMash(names, locs, common, denom,
                          np.load(os.path.join(d, "nhash.npy"), allow_pickle=False),
                          np.load(os.path.join(d, "length.npy"), allow_pickle=False), int(meta["s"]))
+
+
+def sparse_dir(data_folder: str) -> str:
+    return os.path.join(data_folder, SPARSE_SUBDIR)
+
+
+def _write_lines(path: str, items) -> None:
+    with open(path, "w") as fh:
+        for x in items:
+            if "\n" in x:
+                raise ValueError("genome names/locations cannot contain newlines: %r" % x)
+            fh.write(x + "\n")
+
+
+def store_sparse(data_folder: str, sm: SparseMash) -> str:
+    """Write the sparse all-pairs result (d_cluster.SparseMash: the pairs that
+    share a hash) under <data_folder>/MASH_files/sparse/, next to the
+    condensed store: i.npy / j.npy (uint32), common.npy / denom.npy (uint16),
+    one entry per listed pair in (i, j) order, plus nhash.npy, length.npy,
+    names.txt, locations.txt and meta.json as store_condensed writes them."""
+    d = sparse_dir(data_folder)
+    os.makedirs(d, exist_ok=True)
+    n = len(sm.i)
+    if not (len(sm.j) == len(sm.common) == len(sm.denom) == n):
+        raise ValueError("i, j, common and denom must have one entry per pair")
+    for fname, arr, dt in (("i.npy", sm.i, np.uint32), ("j.npy", sm.j, np.uint32), ("common.npy", sm.common, np.uint16),
+                           ("denom.npy", sm.denom, np.uint16), ("nhash.npy", sm.nhash, np.uint32),
+                           ("length.npy", sm.length, np.uint64)):
+        np.save(os.path.join(d, fname), np.ascontiguousarray(arr, dtype=dt))
+    _write_lines(os.path.join(d, "names.txt"), sm.names)
+    _write_lines(os.path.join(d, "locations.txt"), sm.locations)
+    with open(os.path.join(d, "meta.json"), "w") as fh:
+        json.dump({"k": MASH_K, "s": int(sm.s), "seed": MASH_SEED, "N": len(sm.names), "pairs": n,
+                   "layout": "pairs (i, j), i < j, with common > 0, sorted by (i, j); unlisted pairs: common 0"},
+                  fh, indent=1)
+    return d
+
+
+def load_sparse(data_folder: str, mmap: bool = True) -> SparseMash:
+    """Read what store_sparse wrote (the pair arrays memory-mapped by default)."""
+    d = sparse_dir(data_folder)
+    meta = json.load(open(os.path.join(d, "meta.json")))
+    mode = "r" if mmap else None
+
+    def arr(fname):
+        return np.load(os.path.join(d, fname), mmap_mode=mode, allow_pickle=False)
+    names = open(os.path.join(d, "names.txt")).read().split("\n")[:meta["N"]]
+    locs = open(os.path.join(d, "locations.txt")).read().split("\n")[:meta["N"]]
+    return SparseMash(names, locs, arr("i.npy"), arr("j.npy"), arr("common.npy"), arr("denom.npy"),
+                      np.load(os.path.join(d, "nhash.npy"), allow_pickle=False),
+                      np.load(os.path.join(d, "length.npy"), allow_pickle=False), int(meta["s"]))
 
 
 def store_primary_linkage(data_folder: str, linkage: np.ndarray, linkage_db: Any,

@@ -321,6 +321,44 @@ int drephip_allpairs_device_marked(drephip_ctx *ctx, const uint64_t *d_hashes, c
                                    const uint32_t *d_cells, uint64_t n_cells, const uint32_t *d_records,
                                    uint64_t n_records, void *stream);
 
+/* ------------------------------------------------------------ sparse all-pairs
+ * `mash dist` (drep/d_cluster.py:569-573) over rows [row0,row1) of the upper
+ * triangle, listing only the pairs that share a hash: no condensed vector of
+ * N(N-1)/2 entries is written, so N is not bounded by N^2 bytes.  A record is
+ * 4 uint32 {i, j, common, denom}, i < j (genome indices as given), common > 0,
+ * denom as in the condensed output (always filled); a pair that is not listed
+ * has common 0, i.e. Mash distance 1.  Every unordered pair appears at most
+ * once; the order of the records is unspecified.
+ *
+ * The caller provides room for `cap` records.  When the rows hold more, the
+ * call stores the first `cap` reserved slots only (nothing outside [0, cap)),
+ * returns DREPHIP_ERR_NOMEM and sets *n_pairs to the number needed, so one
+ * retry with that size succeeds; cap = 0 (pairs may be NULL) only counts.
+ *
+ * Plans: with the whole-row tables (s <= 2048) and the shared-hash screen in
+ * use (DREPHIP_SCREEN_ON, or DREPHIP_SCREEN_AUTO from 4096 genomes on unless
+ * the set is dense) the screen and the LIST kernel append their non-zero pairs
+ * themselves, walking the rows in blocks so that the screen's scratch stays
+ * inside a budget taken from the device's free memory.  Every other plan (band
+ * path, screen off or dense, N x s >= 2^32, DREPHIP_AP_MERGE) computes a
+ * temporary condensed segment of at most 2^28 pairs per row block inside the
+ * context and compacts its non-zero counts.  The environment variable
+ * DREPHIP_SPARSE_BLOCK_ROWS sets the rows per block of either plan (tests).
+ * drephip_last_screen_stats and drephip_last_kernel_ms describe the call's
+ * screen and kernels as after drephip_allpairs_device.  Blocking. */
+int drephip_allpairs_sparse_device(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash,
+                                   uint32_t N, uint32_t row0, uint32_t row1,
+                                   uint32_t *d_pairs /* cap x 4 */, uint64_t cap, uint64_t *n_pairs, void *stream);
+/* The host form: sketches checked as drephip_allpairs requires them (rows
+ * ascending and distinct, UINT64_MAX past nhash[i]; DREPHIP_ERR_ARG otherwise). */
+int drephip_allpairs_sparse(drephip_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash, uint32_t N,
+                            uint32_t row0, uint32_t row1, uint32_t *pairs /* cap x 4 */, uint64_t cap,
+                            uint64_t *n_pairs);
+/* last sparse call: row blocks walked, pairs from the direct kernels, pairs from the
+ * fallback compaction, peak bytes of context scratch */
+int drephip_last_sparse_stats(drephip_ctx *ctx, uint32_t *blocks, uint64_t *direct, uint64_t *fallback,
+                              uint64_t *scratch_bytes);
+
 /* ---------------------------------------------------------- primary clustering
  * Replaces: scipy.cluster.hierarchy.linkage(squareform(dist), method) in
  * cluster_hierarchical (drep/d_cluster.py:447-453), called from
