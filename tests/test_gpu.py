@@ -1101,7 +1101,7 @@ def test_linkage_counts_device_sparse_vs_dense(ctx1000, partial):
     D = D + D.T
     from scipy.spatial.distance import squareform
     y = squareform(D, checks=False)
-    for method in ("average", "single", "complete"):
+    for method in ("average", "single", "complete", "weighted"):
         Zs = sch.linkage(y, method=method)
         got = {}
         for path in (ctx1000.LINK_SPARSE, ctx1000.LINK_DENSE):
