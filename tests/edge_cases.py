@@ -3,8 +3,10 @@ tests/test_edge_helpers.py (CPU): a set-based all-pairs reference that shares
 no code with the oracle's merge loop, sketch sets built so that the all-pairs
 kernels' data-dependent paths are taken (the hash values 0 and UMAX - 1, shared
 hashes on both sides of union rank s at every column chunk boundary, shared
-hashes late in one sketch and early in the other), and sequence layouts that
-put a k-mer on every boundary of the sketch kernel's packed layout."""
+hashes late in one sketch and early in the other), sequence layouts that
+put a k-mer on every boundary of the sketch kernel's packed layout, and (for
+tests/test_screen_wide.py) sketch sets wider than one marking window of the
+shared-hash screen, with long and colliding runs of equal sort keys."""
 import numpy as np
 
 import oracle
@@ -392,3 +394,371 @@ def pack_layout(genomes, seed):
     valid = np.packbits(val.reshape(-1, 32), axis=1, bitorder="little").view(np.uint32).reshape(-1)
     return (codes.astype(np.uint32), np.ascontiguousarray(valid), np.array(off, np.uint64), np.array(pad, np.uint64),
             np.array(nk, np.uint64))
+
+
+# ---------------------------------------------------------------- the shared-hash screen past one marking window
+# k_screen_mark of drep_amd/csrc/screen.hip: a workgroup ORs a chunk of kMarkChunk runs (of >= 3 entries, in
+# first-genome order) into an LDS window of kMarkTiles row tiles x kMarkCols columns anchored at the first genome
+# g_lo of the chunk's first run (tiles from g_lo // R, columns from g_lo & ~31); marks outside it go to the bitmap
+# directly.  A run whose entry fingerprints (the low 32 - vbits bits of the hashes' high words, used from kFpBits
+# bits on) all agree is marked as one hash.
+MARK_CHUNK, MARK_TILES, MARK_COLS, FP_BITS = 256, 128, 2048, 4
+WIDE_HUBS = (65, 128, 129, 200, 700)
+
+
+def entry_bits(N, s):
+    """vbits of screen_front: the bits an entry index g s + k needs."""
+    return max(1, int(N * s - 1).bit_length())
+
+
+class _Plants:
+    """Sorted rows of random distinct 62-bit values; plant() puts a value into
+    genomes by replacing one entry that was not planted itself and sorting the
+    row again (as tests/test_screen.py::test_screen_light_cells does)."""
+
+    def __init__(self, N, s, rng, partial_every=0):
+        self.rng, self.s = rng, s
+        self.H = np.sort(rng.integers(1, 1 << 62, size=(N, s), dtype=np.uint64), axis=1)
+        assert len(np.unique(self.H)) == N * s
+        self.NH = np.full(N, s, dtype=np.uint32)
+        for g in range(0, N, partial_every) if partial_every else ():
+            self.NH[g] = rng.integers(s // 2, s)
+            self.H[g, self.NH[g]:] = UMAX
+        self.used = set()
+
+    def value(self):
+        while True:
+            v = int(self.rng.integers(1 << 48, 1 << 62))
+            if v not in self.used:
+                return v
+
+    def plant(self, genomes, v):
+        for g in genomes:
+            n = int(self.NH[g])
+            row = self.H[g, :n]
+            assert _U(v) not in row
+            free = [k for k in range(n) if int(row[k]) not in self.used]
+            j = free[int(self.rng.integers(len(free)))]
+            self.H[g, :n] = np.sort(np.concatenate([np.delete(row, j), [_U(v)]]))
+        self.used.add(int(v))
+
+
+def wide_n(R):
+    """Genomes of the wide sets: past the window in tiles and in columns, no multiple of 32."""
+    return MARK_TILES * R + MARK_COLS + 1100
+
+
+def wide_set_a(R, seed, anchor, s=16):
+    """One chunk, so one window, anchored at g_lo = 32 + anchor (c_lo = 32).
+    For the window's last row tile (g_lo // R + 127) and the first tile past
+    it, a run of three {r, col, z} per edge: the tile's first row r with the
+    columns c_lo + 2047 (the window's last), c_lo + 2048 and N - 1, its last
+    row with their neighbours c_lo + 2046, c_lo + 2049, N - 2 -- each of
+    these cells is marked once (a light cell) -- and, for anchor != 0, the
+    last row with the first row's columns as well: those cells are marked by
+    two runs.  Returns H, NH and {g_lo, edges: [(r, col)]}."""
+    rng = np.random.default_rng(seed)
+    N = wide_n(R)
+    p = _Plants(N, s, rng)
+    g_lo = 32 + anchor
+    c_lo = g_lo & ~31
+    p.plant([g_lo, g_lo + 1, g_lo + 2], p.value())
+    edges, k = [], 0
+    for T in (g_lo // R + MARK_TILES - 1, g_lo // R + MARK_TILES):
+        for r, d in ((T * R, 0), (T * R + R - 1, 1)):
+            cols = [c_lo + MARK_COLS - 1 - d, c_lo + MARK_COLS + d, N - 1 - d]
+            if d and anchor:
+                cols += [c_lo + MARK_COLS - 1, c_lo + MARK_COLS, N - 1]
+            for col in cols:
+                z = col + 7 + k if col + 60 < N else c_lo + MARK_COLS + 300 + k
+                p.plant(sorted([r, col, z]), p.value())
+                edges.append((r, col))
+                k += 1
+    return p.H, p.NH, {"g_lo": g_lo, "edges": edges}
+
+
+def wide_set_b(R, seed, s=16):
+    """Many chunks: 700 runs of 3 to 5 genomes whose first genomes lie about 5
+    apart (a chunk of 256 runs spans ~1280 rows: its later runs start past its
+    128 row tiles), the other members anywhere above; 40 runs of the first
+    chunk extended by a row of a later chunk's run and one of its columns (a
+    cell marked directly by the one and through the window of the other);
+    runs of two on cells and on pairs of longer runs; partial sketches every
+    11th genome."""
+    rng = np.random.default_rng(seed)
+    N = wide_n(R)
+    p = _Plants(N, s, rng, partial_every=11)
+    runs = []
+    for i in range(700):
+        f = 5 * i + int(rng.integers(0, 3))
+        runs.append([f] + sorted(int(x) for x in rng.choice(np.arange(f + 1, N), int(rng.integers(2, 5)), replace=False)))
+    for j in range(40):
+        y = 300 + 8 * j
+        fy = runs[y][0]
+        col = fy + 100 + j
+        runs[y] = sorted(set(runs[y]) | {col})
+        row = fy + 1 if (fy + 1) % R else fy                 # a row of fy's tile
+        x = 3 + 6 * j
+        runs[x] = sorted(set(runs[x]) | {row, col})
+    for r in runs:
+        p.plant(r, p.value())
+    for i in range(0, 700, 7):                              # runs of two
+        a, c = runs[i][0], runs[i][-1]
+        if i % 2:
+            p.plant([a, c], p.value())                      # a second hash of a pair of the run
+        else:
+            a2 = [g for g in range(a // R * R, a // R * R + R) if g not in runs[i]][0]
+            p.plant(sorted([a2, c]), p.value())             # another row of the cell
+    return p.H, p.NH, {}
+
+
+def wide_set_c(R, seed, s=16, hubs=WIDE_HUBS):
+    """Long and colliding runs.  A twin of v has v's low word (one sort key,
+    one run): the slow twin v ^ (1 << 33) differs in a fingerprint bit, the
+    equal twin v ^ (1 << 63) -- or another bit from 47 up in the small mixes,
+    so that its rank varies -- has v's fingerprint.
+    - per hub length m: a clean hub, and per twin kind a hub whose entries 0,
+      63, 64 and m - 1 hold the twin;
+    - m = 129 with the single twin at 63, at 64; m = 65 with it at 0, at 64;
+      m = 129 with every other entry holding the twin; each per twin kind;
+    - equal-fingerprint mixes, 8 of each, half on neighbouring genomes (one
+      row tile), half spread: {v, v, v'} with v' in the first, second, third
+      genome; {v, v, v', v'} in three orders; a genome holding v and v' with
+      two others holding v, or holding v', the double genome first, second,
+      third."""
+    rng = np.random.default_rng(seed)
+    N = wide_n(R)
+    p = _Plants(N, s, rng)
+
+    def hub(m, twin_at, bit):
+        g = np.sort(rng.choice(N, m, replace=False))
+        v = p.value()
+        tw = np.zeros(m, dtype=bool)
+        tw[list(twin_at)] = True
+        p.plant(g[~tw], v)
+        if tw.any():
+            p.plant(g[tw], v ^ (1 << bit))
+
+    for m in hubs:
+        hub(m, (), 0)
+        for bit in (33, 63):
+            hub(m, (0, 63, 64, m - 1), bit)
+    for bit in (33, 63):
+        for m, at in ((129, 63), (129, 64), (65, 0), (65, 64)):
+            hub(m, (at,), bit)
+        hub(129, range(1, 129, 2), bit)
+    for rep in range(8):
+        def genomes(n):
+            if rep % 2:
+                return np.sort(rng.choice(N, n, replace=False))
+            g0 = int(rng.integers(0, N - 2 * n))
+            return np.arange(g0, g0 + n)
+        bit = 63 if rep < 2 else int(rng.integers(47, 62))
+        for n, who in ((3, (0,)), (3, (1,)), (3, (2,)), (4, (2, 3)), (4, (1, 3)), (4, (0, 3))):
+            g = genomes(n)
+            v = p.value()
+            p.plant(np.delete(g, who), v)
+            p.plant(g[list(who)], v ^ (1 << bit))
+        for both in (0, 1, 2):
+            for others_twin in (False, True):
+                g = genomes(3)
+                v = p.value()
+                p.plant([g[both]], v)
+                p.plant([g[both]], v ^ (1 << bit))
+                p.plant(np.delete(g, both), v ^ (1 << bit) if others_twin else v)
+    return p.H, p.NH, {}
+
+
+def wide_screen_sets(R, seed):
+    """The sketch sets of tests/test_screen_wide.py at s = 16, by name: A0, A1,
+    A31 (wide_set_a with that anchor), B, C (wide_set_b, wide_set_c) as (H, NH,
+    info).  R: rows per row tile (Context.screen_geometry())."""
+    sets = {"A%d" % a: wide_set_a(R, seed + a, a) for a in (0, 1, 31)}
+    sets["B"] = wide_set_b(R, seed + 100)
+    sets["C"] = wide_set_c(R, seed + 200)
+    return sets
+
+
+def mark_emulation(H, NH, s, R):
+    """What k_screen_mark does with a sketch set, counted: the entries grouped
+    by low word, the runs of >= 3 ordered by (first genome, key) and cut into
+    chunks of MARK_CHUNK, each run's cells (row tile of the smaller genome,
+    larger genome) -- every entry pair of a run whose fingerprints agree (all
+    hashes, below FP_BITS fingerprint bits), else the pairs of equal hashes --
+    sorted into window and direct marks by its chunk's window.  Returns a dict
+    of counts (see the keys below)."""
+    N = len(NH)
+    fbits = 32 - entry_bits(N, s)
+    g = np.repeat(np.arange(N), NH)
+    k = np.concatenate([np.arange(n) for n in NH])
+    h = H[g, k]
+    key = (h & _U(0xFFFFFFFF)).astype(np.int64)
+    o = np.argsort(key, kind="stable")
+    g, k, h, key = g[o], k[o], h[o], key[o]
+    heads = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]]))
+    ends = np.concatenate([heads[1:], [len(key)]])
+    full = NH == s
+    st = dict.fromkeys(("runs3", "chunks", "in_in", "in_out", "out_in", "out_out", "edge_tile_127", "edge_tile_128",
+                        "edge_col_2047", "edge_col_2048", "direct_once_same", "direct_twice", "window_twice",
+                        "window_and_direct", "window_overhang", "two_on_long_cell", "two_on_long_pair",
+                        "equal_fp_mixed", "equal_fp_mixed_long", "slow_long", "diagonal", "dup_second_shared",
+                        "light_other_hash_low_rank", "rank_below_s", "rank_from_s"), 0)
+    st["twin_at"] = set()
+    long_runs = [(int(g[a]), int(key[a]), a, e) for a, e in zip(heads, ends) if e - a >= 3]
+    long_runs.sort()
+    st["runs3"] = len(long_runs)
+    st["chunks"] = (len(long_runs) + MARK_CHUNK - 1) // MARK_CHUNK
+    cells, chunk_of, inwin, same_of = [], [], [], []
+    other_hash = []                                          # cells of pairs a light cell must not count
+    for q, (_, _, a, e) in enumerate(long_runs):
+        if q % MARK_CHUNK == 0:
+            g_lo = long_runs[q][0]
+            t_lo, c_lo = g_lo // R, g_lo & ~31
+            st["window_overhang"] += (t_lo + MARK_TILES) * R > N or c_lo + MARK_COLS > N
+        gs, hs, ks = g[a:e], h[a:e], k[a:e]
+        m = e - a
+        if fbits >= FP_BITS:
+            fp = (hs >> _U(32)) & _U((1 << fbits) - 1)
+            same = bool((fp == fp[0]).all())
+        else:
+            same = bool((hs == hs[0]).all())
+        mixed = not (hs == hs[0]).all()
+        xi, yi = np.triu_indices(m, 1)
+        share = (hs[xi] == hs[yi]) & (gs[xi] != gs[yi])
+        if same:
+            st["equal_fp_mixed"] += mixed
+            st["equal_fp_mixed_long"] += mixed and m > 64
+            st["diagonal"] += bool((gs[1:] == gs[:-1]).any())
+            dup = np.flatnonzero(gs[1:] == gs[:-1]) + 1     # second entries of genomes that hold two
+            st["dup_second_shared"] += int(sum(((hs == hs[d]) & (gs != gs[d])).any() and hs[d] != hs[d - 1] for d in dup))
+            wrong = ~share & (gs[xi] != gs[yi]) & full[gs[xi]] & full[gs[yi]] & (ks[xi] + ks[yi] < s)
+            other_hash.append((gs[xi][wrong] // R) * N + gs[yi][wrong])
+            keep = np.ones(len(xi), dtype=bool)
+        else:
+            st["slow_long"] += m > 64
+            keep = share
+        if mixed and m > 64:
+            vals, cnt = np.unique(hs, return_counts=True)
+            st["twin_at"] |= {(int(p), "equal" if same else "slow") for p in np.flatnonzero(hs == vals[np.argmin(cnt)])
+                              if cnt.min() <= 4}
+        one = share & full[gs[xi]] & full[gs[yi]]
+        st["rank_below_s"] += int((one & (ks[xi] + ks[yi] < s)).sum())
+        st["rank_from_s"] += int((one & (ks[xi] + ks[yi] >= s)).sum())
+        c = np.unique((gs[xi][keep] // R) * N + gs[yi][keep])
+        t, col = c // N, c % N
+        w = (t - t_lo < MARK_TILES) & (col - c_lo < MARK_COLS)
+        st["in_in"] += int(w.sum())
+        st["in_out"] += int(((t - t_lo < MARK_TILES) & ~(col - c_lo < MARK_COLS)).sum())
+        st["out_in"] += int((~(t - t_lo < MARK_TILES) & (col - c_lo < MARK_COLS)).sum())
+        st["out_out"] += int((~(t - t_lo < MARK_TILES) & ~(col - c_lo < MARK_COLS)).sum())
+        st["edge_tile_127"] += int((t - t_lo == MARK_TILES - 1).sum())
+        st["edge_tile_128"] += int((t - t_lo == MARK_TILES).sum())
+        st["edge_col_2047"] += int((col - c_lo == MARK_COLS - 1).sum())
+        st["edge_col_2048"] += int((col - c_lo == MARK_COLS).sum())
+        cells.append(c)
+        chunk_of.append(np.full(len(c), q // MARK_CHUNK))
+        inwin.append(w)
+        same_of.append(np.full(len(c), same))
+    if not cells:
+        return st
+    cells, chunk_of, inwin, same_of = (np.concatenate(x) for x in (cells, chunk_of, inwin, same_of))
+    uc, inv, cnt = np.unique(cells, return_inverse=True, return_counts=True)
+    once = cnt[inv] == 1
+    st["direct_once_same"] = int((once & ~inwin & same_of).sum())
+    nwin = np.bincount(inv, weights=inwin, minlength=len(uc))
+    ndir = cnt - nwin
+    st["direct_twice"] = int((ndir >= 2).sum())
+    st["window_twice"] = int((nwin >= 2).sum())
+    for u in np.flatnonzero((nwin >= 1) & (ndir >= 1)):
+        sel = inv == u
+        st["window_and_direct"] += len(set(chunk_of[sel][inwin[sel]]) ^ set(chunk_of[sel][~inwin[sel]])) > 0
+    if other_hash:
+        oh = np.unique(np.concatenate(other_hash))
+        at = np.searchsorted(uc, oh)
+        st["light_other_hash_low_rank"] = int((cnt[at] == 1).sum())
+    for a, e in zip(heads, ends):                            # runs of two that hold one hash in two genomes
+        if e - a == 2 and h[a] == h[a + 1] and g[a] != g[a + 1]:
+            c = (g[a] // R) * N + g[a + 1]
+            at = np.searchsorted(uc, c)
+            st["two_on_long_cell"] += bool(at < len(uc) and uc[at] == c)
+    pairs = {}                                               # (short runs only: the sets plant these on runs of <= 6)
+    for a, e in zip(heads, ends):
+        if 2 <= e - a <= 6:
+            for x in range(a, e):
+                for y in range(x + 1, e):
+                    if h[x] == h[y] and g[x] != g[y]:
+                        pairs.setdefault((int(g[x]), int(g[y])), []).append(e - a)
+    st["two_on_long_pair"] = sum(1 for v in pairs.values() if 2 in v and max(v) >= 3)
+    return st
+
+
+# ---------------------------------------------------------------- no fingerprint: N s > 2^28
+SHORT_N, SHORT_S, SHORT_MAX = 8200, 32767, 16
+
+
+def short_row_sets(seed, N=SHORT_N, nmax=SHORT_MAX):
+    """N partial sketches of at most nmax hashes (rows [N, nmax], UMAX past
+    NH): hubs of 70 and 200 genomes over the whole of 0 .. N - 1 (the last
+    genome among them), a collision run of 100 genomes that hold v and
+    v ^ (1 << 63) in turn, one of 90 with v and v ^ (1 << 33), 300 triples, 300
+    runs of two, low-word twins."""
+    rng = np.random.default_rng(seed)
+    rows = [set(int(x) for x in rng.integers(1, 1 << 62, size=int(rng.integers(2, 9)))) for _ in range(N)]
+
+    def plant(gs, v):
+        for x in gs:
+            if len(rows[x]) < nmax:
+                rows[x].add(int(v))
+
+    def some(m, last=False):
+        gs = rng.choice(N - 1, m, replace=False)
+        return np.concatenate([gs[1:], [N - 1]]) if last else gs
+    plant(some(70), rng.integers(1, 1 << 62))
+    plant(some(200, last=True), rng.integers(1, 1 << 62))
+    for m, bit in ((100, 63), (90, 33)):
+        gs, v = np.sort(some(m)), int(rng.integers(1 << 48, 1 << 62))
+        plant(gs[0::2], v)
+        plant(gs[1::2], v ^ (1 << bit))
+    for _ in range(300):
+        plant(some(3), rng.integers(1, 1 << 62))
+        plant(some(2), rng.integers(1, 1 << 62))
+    for _ in range(50):
+        a, b = some(2)
+        v = int(rng.integers(1 << 48, 1 << 62))
+        plant([a], v)
+        plant([b], v ^ (1 << int(rng.integers(32, 64))))
+    H = np.full((N, nmax), UMAX, dtype=np.uint64)
+    NH = np.zeros(N, dtype=np.uint32)
+    for x, r in enumerate(rows):
+        H[x, :len(r)] = np.sort(np.array(sorted(r), dtype=np.uint64))
+        NH[x] = len(r)
+    return H, NH
+
+
+def incidence_allpairs(H, NH):
+    """(common, denom) condensed of sketches so short that no pair's union
+    reaches s (|A u B| <= |A| + |B| < s): common = |A n B|, denom = |A| + |B| -
+    |A n B|, from the incidence matrix of the distinct values."""
+    import scipy.sparse as sp
+    N = len(NH)
+    n = NH.astype(np.int64)
+    vals = np.concatenate([H[x, :n[x]] for x in range(N)])
+    _, inv = np.unique(vals, return_inverse=True)
+    M = sp.csr_matrix((np.ones(len(inv), np.int32), (np.repeat(np.arange(N), n), inv)), shape=(N, int(inv.max()) + 1))
+    S = sp.triu(M @ M.T, 1).tocsr()
+    S.sort_indices()
+    S = S.tocoo()                                            # in (i, j) order
+    common = np.zeros(N * (N - 1) // 2, dtype=np.uint16)
+    denom = np.empty(N * (N - 1) // 2, dtype=np.uint16)
+    for i in range(N - 1):
+        o = cond_index(i, i + 1, N)
+        denom[o:o + N - 1 - i] = n[i] + n[i + 1:]
+    t = cond_index(S.row.astype(np.int64), S.col.astype(np.int64), N)
+    common[t] = S.data
+    denom[t] -= S.data.astype(np.uint16)
+    return common, denom, S.row.astype(np.uint32), S.col.astype(np.uint32)
+
+
+def cell_count(i, j, N, R):
+    """Distinct cells (row tile of i, column j) of the pairs (i, j)."""
+    return len(np.unique((i // R).astype(np.int64) * N + j))

@@ -1,7 +1,9 @@
 """CPU checks of tests/edge_cases.py: the set-based all-pairs reference
 equals the oracle's merge on every generator, the generators produce the
-conditions the GPU tests rely on, and the plain-Python sketch reference equals
-the oracle's sketch on the boundary layouts."""
+conditions the GPU tests rely on, the plain-Python sketch reference equals
+the oracle's sketch on the boundary layouts, and the wide screen sets put marks
+inside and outside the marking window and hold the colliding runs they
+promise."""
 import numpy as np
 import pytest
 
@@ -109,6 +111,105 @@ def test_planted_rank_pairs_cycled_m():
     assert 3 * (~pp["zero"]).sum() <= (~full["zero"]).sum() + 6 and set(pp["m"].tolist()) == set(ec.RANK_M)
     assert set(pp["j"].tolist()) == set(full["j"].tolist())
     assert pp["zero"].sum() == full["zero"].sum() > 0
+
+
+def _rows_ascending(H, NH):
+    n = NH.astype(np.int64)[:, None]
+    k = np.arange(H.shape[1])[None, :]
+    inside = k < n
+    assert (H[~inside] == UMAX).all() and (H[inside] != UMAX).all()
+    assert ((H[:, 1:] > H[:, :-1]) | ~inside[:, 1:]).all()
+
+
+@pytest.mark.parametrize("R", [8, 4])
+def test_wide_screen_sets_categories(R):
+    """The wide sets put marks where tests/test_screen_wide.py needs them, by
+    an emulation of the screen's grouping and marking (ec.mark_emulation)."""
+    s = 16
+    sets = ec.wide_screen_sets(R, seed=7)
+    N = ec.wide_n(R)
+    assert N % 32 and N > ec.MARK_TILES * R + ec.MARK_COLS + 32
+    for name, (H, NH, info) in sets.items():
+        assert H.shape == (N, s)
+        _rows_ascending(H, NH)
+        st = ec.mark_emulation(H, NH, s, R)
+        if name[0] == "A":
+            assert st["chunks"] == 1 and 3 <= st["runs3"] < ec.MARK_CHUNK, (name, st)
+            assert info["g_lo"] % 32 == int(name[1:])
+            # every combination of in / out by tile and by column, on the very edges
+            for k in ("in_in", "in_out", "out_in", "out_out", "edge_tile_127", "edge_tile_128", "edge_col_2047",
+                      "edge_col_2048", "direct_once_same"):
+                assert st[k] >= 1, (name, k, st)
+            assert (st["direct_twice"] >= 6 and st["window_twice"] >= 1) or name == "A0", (name, st)
+            t_in = info["g_lo"] // R + ec.MARK_TILES - 1
+            c_lo = info["g_lo"] & ~31
+            want = {(t, c) for t in (t_in, t_in + 1) for c in (c_lo + ec.MARK_COLS - 1, c_lo + ec.MARK_COLS, N - 1)}
+            assert want <= {(r // R, c) for r, c in info["edges"]}
+            assert {r % R for r, _ in info["edges"]} == {0, R - 1}
+        if name == "B":
+            assert st["chunks"] == 3 and 690 <= st["runs3"] <= 710, st
+            for k in ("in_in", "in_out", "out_in", "out_out", "direct_once_same", "direct_twice", "window_twice",
+                      "window_and_direct", "window_overhang", "two_on_long_cell", "two_on_long_pair", "rank_below_s",
+                      "rank_from_s"):
+                assert st[k] >= 1, (name, k, st)
+            assert (NH[::11] < s).all() and (np.delete(NH, np.arange(0, N, 11)) == s).all()
+        if name == "C":
+            for k in ("in_in", "in_out", "out_in", "out_out", "equal_fp_mixed", "equal_fp_mixed_long", "slow_long",
+                      "diagonal", "dup_second_shared", "light_other_hash_low_rank", "rank_below_s", "rank_from_s"):
+                assert st[k] >= 1, (name, k, st)
+            for kind in ("slow", "equal"):
+                assert {(p, kind) for p in (0, 63, 64, 127, 128, 199, 699)} <= st["twin_at"], st["twin_at"]
+    # the same categories of set C with R = 4 rows per tile at s = 64
+    H, NH, _ = ec.wide_set_c(4, 9, s=64)
+    _rows_ascending(H, NH)
+    st = ec.mark_emulation(H, NH, 64, 4)
+    for k in ("equal_fp_mixed_long", "slow_long", "diagonal", "dup_second_shared", "light_other_hash_low_rank"):
+        assert st[k] >= 1, (k, st)
+
+
+_WIDE_REF = [("A0", None), ("A1", None), ("A31", None), ("B", None), ("C", ec.WIDE_HUBS[:-1])]
+
+
+@pytest.mark.parametrize("name,hubs", _WIDE_REF, ids=[n for n, _ in _WIDE_REF])
+def test_ref_allpairs_equals_oracle_on_wide_sets(name, hubs):
+    """The oracle, the GPU tests' reference on the wide sets, against the
+    set-based reference (set C without its 700-genome hubs: ref_allpairs
+    walks every sharing pair in Python)."""
+    s, R = 16, 8
+    H, NH, _ = ec.wide_set_c(R, 207, s, hubs) if hubs else ec.wide_screen_sets(R, 7)[name]
+    oc, od = oracle.allpairs(H, NH, s, threads=8)
+    assert (oc > 0).sum() < 200_000
+    rc, rd = ec.ref_allpairs(H, NH, s)
+    assert np.array_equal(rc, oc) and np.array_equal(rd, od)
+
+
+def test_short_row_sets_and_incidence_reference():
+    """The no-fingerprint case's rows: at most 16 hashes, N s > 2^28 (fewer
+    than FP_BITS fingerprint bits), more than 8192 genomes; its reference
+    (counts from the incidence matrix) equals the oracle at s = 64, where no
+    union of two rows reaches s either."""
+    H, NH = ec.short_row_sets(seed=3)
+    N = len(NH)
+    assert N == ec.SHORT_N > 8192 and N * ec.SHORT_S > 1 << 28 and 32 - ec.entry_bits(N, ec.SHORT_S) < ec.FP_BITS
+    assert N * ec.SHORT_S < 1 << 32 and 1 <= NH.min() and NH.max() <= ec.SHORT_MAX and 2 * ec.SHORT_MAX < 64
+    _rows_ascending(H, NH)
+    H64 = np.full((N, 64), UMAX, dtype=np.uint64)
+    H64[:, :ec.SHORT_MAX] = H
+    c, d, i, j = ec.incidence_allpairs(H, NH)
+    oc, od = oracle.allpairs(H64, NH, 64, threads=8)
+    assert np.array_equal(c, oc) and np.array_equal(d, od)
+    assert np.array_equal(ec.cond_index(i.astype(np.int64), j.astype(np.int64), N), np.flatnonzero(c))
+    # hubs reach the last genome and the columns past 8192; runs longer than a wave whose hashes differ
+    assert j.max() == N - 1 and (j > 8192).sum() >= 5 and c.max() >= 2
+    st = ec.mark_emulation(H, NH, ec.SHORT_S, 4)
+    assert st["slow_long"] == 2 and st["equal_fp_mixed"] == 0 and st["runs3"] >= 300, st
+    vals = np.sort(H[H != UMAX])
+    lo = vals & np.uint64(0xFFFFFFFF)
+    order = np.lexsort((vals, lo))
+    twins = (lo[order][1:] == lo[order][:-1]) & (vals[order][1:] != vals[order][:-1])
+    # low-word twins that agree in the 3 fingerprint bits the entry values still hold: only the hash read tells them apart
+    fp = (vals[order] >> np.uint64(32)) & np.uint64(7)
+    assert twins.sum() >= 50 and (twins & (fp[1:] == fp[:-1])).sum() >= 1
 
 
 def test_boundary_genomes_layout_and_reference():
