@@ -67,6 +67,7 @@ SIGNATURES = {
     "drephip_sketch_wait": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "drephip_synth_device": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                        vp, vp, vp]),
+    "drephip_prefilter_eval": (C.c_int, [u64p, u64p, C.c_uint64, C.c_uint64, u8p, u8p]),
     "drephip_allpairs": (C.c_int, [vp, u64p, u32p, C.c_uint32, u16p, vp]),
     "drephip_allpairs_rows": (C.c_int, [vp, u64p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
     "drephip_allpairs_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]),
@@ -218,6 +219,22 @@ def distance_lut(denom: int, k: int = 21) -> np.ndarray:
     out = np.zeros(denom + 1, dtype=np.float64)
     check(lib().drephip_distance_lut(k, denom, out), "drephip_distance_lut")
     return out
+
+
+def prefilter_eval(q1: np.ndarray, q2: np.ndarray, T: int) -> Tuple[np.ndarray, np.ndarray]:
+    """drephip_prefilter_eval (host): (pass, exact) bits of the sketch kernel's
+    reject-early test and of h1 <= T for the fmix64 state pairs (q1, q2)."""
+    q1 = np.ascontiguousarray(q1, dtype=np.uint64)
+    q2 = np.ascontiguousarray(q2, dtype=np.uint64)
+    if q1.shape != q2.shape or q1.ndim != 1:
+        raise ValueError("q1 and q2 must be equal-length vectors")
+    n = len(q1)
+    ok = np.zeros(max(n, 1), np.uint8)
+    exact = np.zeros(max(n, 1), np.uint8)
+    z = np.zeros(1, np.uint64)
+    check(lib().drephip_prefilter_eval(q1 if n else z, q2 if n else z, n, int(T), ok, exact),
+          "drephip_prefilter_eval")
+    return ok[:n].astype(bool), exact[:n].astype(bool)
 
 
 def write_mash_table(path: str, names: Sequence[str], common: np.ndarray, denom: Optional[np.ndarray], s: int,

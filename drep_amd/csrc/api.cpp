@@ -3,6 +3,7 @@
 // threads for FASTA ingest.  All sketch/dist arithmetic runs in the HIP
 // kernels of sketch.hip and allpairs.hip.
 #include "ctx.h"
+#include "prefilter.h"
 #include "../../include/drephip.h"
 
 #include <algorithm>
@@ -950,6 +951,19 @@ DREPHIP_EXPORT int drephip_distance_lut(int k, uint32_t denom, double *lut) {
             if (d > 1.0) d = 1.0;
         }
         lut[c] = d;
+    }
+    return DREPHIP_OK;
+}
+
+// The sketch kernel's prefilter on the host (prefilter.h: the inline functions
+// k_sketch_hash21 calls), for tests/test_sketch_prefilter.py
+DREPHIP_EXPORT int drephip_prefilter_eval(const uint64_t *q1, const uint64_t *q2, uint64_t n, uint64_t T,
+                                          uint8_t *pass, uint8_t *exact) {
+    if (n && (!q1 || !q2 || !pass || !exact)) { set_error("bad argument"); return DREPHIP_ERR_ARG; }
+    const uint32_t Tp = prefilter_bound(T);
+    for (uint64_t i = 0; i < n; i++) {
+        pass[i] = prefilter_hi(q1[i], q2[i]) <= Tp;
+        exact[i] = murmur_fin(q1[i], q2[i]) <= T;
     }
     return DREPHIP_OK;
 }

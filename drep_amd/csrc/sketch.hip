@@ -24,6 +24,7 @@
 // HBM traffic is 3 bits/base (0.375 B/base) plus the candidate sets.
 
 #include "ctx.h"
+#include "prefilter.h"
 #include "../../include/drephip.h"
 
 #include <algorithm>
@@ -72,22 +73,10 @@ __device__ __forceinline__ uint64_t add64(uint64_t a, uint64_t b) {   // one v_l
     asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(y) : "v"(a), "v"(b));
     return y;
 }
-// fmix64 up to its last multiply: q = ((k ^ k >> 33) C1) ^ (... >> 33); the
-// state before fmix64's final xorshift is then q C2 (fmix_mul)
-constexpr uint64_t kFmixC2 = 0xc4ceb9fe1a85ec53ULL;
-__device__ __forceinline__ uint64_t fmix64_q(uint64_t k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL;
-    k ^= k >> 33;
-    return k;
-}
-__device__ __forceinline__ uint64_t fmix_mul(uint64_t q) { return q * kFmixC2; }
-// hi(q1 C2) + hi(q2 C2) + 1 (mod 2^32) with the multiplies shared:
-// hi(q C2) = hi(lo q lo C2) + lo q hi C2 + hi q lo C2
-__device__ __forceinline__ uint32_t prefilter_hi(uint64_t q1, uint64_t q2) {
-    const uint32_t a1 = (uint32_t)q1, b1 = (uint32_t)(q1 >> 32), a2 = (uint32_t)q2, b2 = (uint32_t)(q2 >> 32);
-    return __umulhi(a1, (uint32_t)kFmixC2) + __umulhi(a2, (uint32_t)kFmixC2) + (a1 + a2) * (uint32_t)(kFmixC2 >> 32) +
-           (b1 + b2) * (uint32_t)kFmixC2 + 1u;
-}
+// fmix64's tail (fmix64_q, fmix_mul, murmur_fin) and the prefilter
+// (prefilter_bound, prefilter_hi) live in prefilter.h, shared with the host
+// evaluator: the prefilter tests hi((q1 + q2) C2) + 1 <= hi(T) + 2, one 64-bit
+// add and one high-word product, a necessary condition for h1 <= T
 // Candidates are staged in an LDS buffer (wave-aggregated LDS atomic) and only
 // flushed to the per-genome set after the tile, so the hot loop issues no
 // global memory operation with a wait; a full buffer spills to the set
@@ -211,13 +200,14 @@ __device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) { 
 
 // Murmur h1 of the canonical k-mer (top-aligned codes hi:lo), returned as the
 // two fmix64 states q1, q2 before their last multiply: with p = q C2,
-// h1 = fin(p1) + fin(p2), fin(k) = k ^ (k >> 33).  fin leaves the high word
-// unchanged, so
-//     h1 <= T  implies  hi(p1) + hi(p2) + 1  <=  hi(T) + 1   (mod 2^32)
-// (the low-word sum carries at most 1 into the high word; both sides are
-// taken one past so a wrapping 0xFFFFFFFF + carry = 0 is kept): the prefilter
-// (prefilter_hi, the two high words with shared multiplies, and a compare);
-// the exact test runs in the rare admit branch.
+// h1 = fin(p1) + fin(p2), fin(k) = k ^ (k >> 33).  C2 multiplies linearly, so
+// p1 + p2 = (q1 + q2) C2 = P, and fin leaves the high word unchanged, so hi(P)
+// and hi(h1) differ only by the two low-word carries (-1, 0 or +1):
+//     h1 <= T  implies  hi(P) + 1  <=  hi(T) + 2   (mod 2^32; hi(T) <= 0xFFFFFFFD)
+// (both sides one past, so hi(h1) = 0 under hi(P) = 0xFFFFFFFF is kept; above
+// that hi(T) the bound is all ones and nothing is rejected): the prefilter
+// (prefilter.h: one v_lshl_add_u64, the high word of one product, a compare;
+// derivation there); the exact test runs in the rare admit branch.
 // the five table entries of one k-mer
 struct MEnt { u32x4 e1; u32x2 f1; u32x4 e2; u32x2 f2; uint64_t k3; };
 // Table addresses are byte index << entry size.  The shift amounts come in
@@ -293,11 +283,6 @@ __device__ __forceinline__ void murmur21_q(const SketchTablesQ &tb, uint32_t hi,
                                            uint32_t sh, uint64_t &q1, uint64_t &q2) {
     murmur21_ent(fetch_ent(tb, hi, lo, sh), seed, q1, q2);
 }
-__device__ __forceinline__ uint64_t murmur_fin(uint64_t q1, uint64_t q2) {
-    const uint64_t p1 = fmix_mul(q1), p2 = fmix_mul(q2);
-    return add64(p1 ^ (p1 >> 33), p2 ^ (p2 >> 33));
-}
-
 #ifndef DREPHIP_SK_BATCH
 #define DREPHIP_SK_BATCH 2          // k-mers per admit test: 52 VGPRs (4: 58, 0.8 % slower; 8: 73, 7 waves, 2 % slower;
                                     // all 16 of a chunk as one block, keeping only the prefilter bits and recomputing
@@ -329,8 +314,7 @@ __global__ __launch_bounds__(kTile / LANE, DREPHIP_SK_MINW) void k_sketch_hash21
     const uint32_t t = blockIdx.x;
     const uint32_t g = tile_genome[t];
     const uint64_t T = thr[g];
-    const uint32_t Thi = (uint32_t)(T >> 32);
-    const uint32_t Tp = Thi == 0xFFFFFFFFu ? Thi : Thi + 1;     // prefilter bound (see murmur21_q)
+    const uint32_t Tp = prefilter_bound(T);          // hi(T) + 2, saturating (prefilter.h)
     const uint64_t start = tile_base[t] + (uint64_t)threadIdx.x * LANE;
     const uint32_t mask = (1u << set_log2) - 1;
     unsigned long long *S = sets + ((uint64_t)g << set_log2);

@@ -175,6 +175,16 @@ int drephip_synth_device(drephip_ctx *ctx, uint64_t seed, uint32_t g0, uint32_t 
                          uint32_t family_size, uint64_t L, uint32_t *d_codes, uint32_t *d_valid,
                          void *stream);
 
+/* The sketch hash kernel's reject-early test, evaluated on the host through the
+ * inline functions the kernel calls (drep_amd/csrc/prefilter.h; no context, no
+ * GPU).  A k-mer reaches the test as the two fmix64 states before their last
+ * multiply, (q1, q2); its hash is h1 = fin(q1 C2) + fin(q2 C2), fin(p) =
+ * p ^ (p >> 33).  For each of the n pairs and the threshold T: pass[i] = the
+ * prefilter lets the k-mer through to the exact test, exact[i] = h1 <= T.
+ * The prefilter is a necessary condition: exact implies pass. */
+int drephip_prefilter_eval(const uint64_t *q1, const uint64_t *q2, uint64_t n, uint64_t T,
+                           uint8_t *pass, uint8_t *exact);
+
 /* ---------------------------------------------------------------- dist
  * Replaces: `mash dist -p P ALL.msh ALL.msh > MASH_table.tsv`
  * (drep/d_cluster.py:569-573) for the integer part of every row: the shared-

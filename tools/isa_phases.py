@@ -6,7 +6,7 @@ hash blocks to the source function its .loc names -- the k-mer cut and
 canonical select, the table addressing, MurmurHash3's body, fmix64, the
 prefilter -- or to the loop (code-word sliding, validity, branches).  The
 rare admit branch (murmur_fin, the exact test, the staging) is listed apart.
-usage: python tools/isa_phases.py > profiles/r05_sketch_isa_phases.json"""
+usage: [EXTRA=<hipcc flags of an A/B build>] python tools/isa_phases.py > profiles/r05_sketch_isa_phases.json"""
 import collections
 import json
 import os
@@ -16,10 +16,15 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "drep_amd/csrc/sketch.hip")
+HDR = os.path.join(ROOT, "drep_amd/csrc/prefilter.h")      # fmix64's tail and the prefilter (host + device)
 
 
-def func_ranges(lines):
-    """(first, last) source lines of the functions and regions the phases name."""
+PREFILTER = "prefilter (sum, one high word, compare)"
+
+
+def func_ranges(lines, hlines):
+    """(first, last) source lines of the functions and regions the phases name
+    (sketch.hip; negative line numbers: prefilter.h)."""
     def find(pat, start=0):
         for i in range(start, len(lines)):
             if re.search(pat, lines[i]):
@@ -35,24 +40,28 @@ def func_ranges(lines):
     r["table addressing + LDS reads"] = body(r"MEnt fetch_ent\(")
     r["Murmur body (tables combined)"] = body(r"void murmur21_ent\(")
     r["Murmur helpers (rotl, *5+c, add64, mad64)"] = None   # several functions, below
-    r["fmix64 to the last multiply"] = body(r"uint64_t fmix64_q\(")
-    r["prefilter (two high words, compare)"] = body(r"uint32_t prefilter_hi\(")
+    def hbody(pat):                      # a function of prefilter.h, as negated line numbers
+        a = next(i + 1 for i in range(len(hlines)) if re.search(pat, hlines[i]))
+        b = next(i + 1 for i in range(a, len(hlines)) if hlines[i].startswith("}"))
+        return -b, -a
+    r["fmix64 to the last multiply"] = hbody(r"uint64_t fmix64_q\(")
+    r[PREFILTER] = [hbody(p) for p in (r"uint32_t prefilter_hi\(", r"uint32_t mulhi32\(")]
     r["admit branch (rare)"] = (find(r"if \(__builtin_expect\(hit, 0\)\)"), find(r"// slide one code word") - 1)
     helpers = [body(p) for p in (r"uint64_t rotl64_ab\(", r"uint64_t x5_plus\(", r"uint64_t add64\(",
                                  r"uint64_t mad64\(")]
     r["Murmur helpers (rotl, *5+c, add64, mad64)"] = helpers
-    r["murmur_fin (admit branch)"] = body(r"uint64_t murmur_fin\(")
+    r["murmur_fin (admit branch)"] = [hbody(r"uint64_t murmur_fin\("), hbody(r"uint64_t fmix_mul\(")]
     return r
 
 
 def main():
     lines = open(SRC).read().split("\n")
-    ranges = func_ranges(lines)
+    ranges = func_ranges(lines, open(HDR).read().split("\n"))
     hit_line = next(i + 1 for i, l in enumerate(lines) if "hit |= prefilter_hi" in l)
 
     def phase_of(line):
         if line == hit_line:
-            return "prefilter (two high words, compare)"
+            return PREFILTER
         for name, rg in ranges.items():
             for a, b in (rg if isinstance(rg, list) else [rg]):
                 if a <= line <= b:
@@ -61,13 +70,15 @@ def main():
     with tempfile.TemporaryDirectory() as td:
         asm = os.path.join(td, "sk.s")
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-gline-tables-only",
-                        "--cuda-device-only", "-S", "-o", asm, SRC, "-I" + os.path.join(ROOT, "drep_amd/csrc")],
-                       check=True, stderr=subprocess.DEVNULL)
+                        "--cuda-device-only", "-S", "-o", asm, SRC, "-I" + os.path.join(ROOT, "drep_amd/csrc")] +
+                       os.environ.get("EXTRA", "").split(), check=True, stderr=subprocess.DEVNULL)
         s = open(asm).read()
-    fileno = None
+    fileno = hdrno = None
     for m in re.finditer(r'^\s*\.file\s+(\d+)\s+"[^"]*"\s+"([^"]*)"', s, re.M):
         if m.group(2).endswith("sketch.hip"):
             fileno = m.group(1)
+        if m.group(2).endswith("prefilter.h"):
+            hdrno = m.group(1)
     m = re.search(r"^(_ZN7drephip\d+k_sketch_hash21ILi64ELi2E\S*):", s, re.M)
     body = s[m.start():s.index(".Lfunc_end", m.start())]
     # blocks between labels; the hot ones hold the hash (2 k-mers' mad_u64 chains)
@@ -80,7 +91,7 @@ def main():
             continue
         lm = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
         if lm:
-            loc = int(lm.group(2)) if lm.group(1) == fileno else 0
+            loc = int(lm.group(2)) if lm.group(1) == fileno else -int(lm.group(2)) if lm.group(1) == hdrno else 0
             continue
         if cur is None or not ln.startswith("\t") or t.startswith((".", ";")) or not t:
             continue

@@ -11,7 +11,8 @@ assembly, the unrolled hash blocks: tools/isa_count.py's selection), every
 instruction is priced at its class's measured rate, and the sum over one k-mer
 times the k-mers per SIMD is the predicted time.
 
-usage: python tools/sketch_priced.py <dir with the GPU outputs> > profiles/r06_sketch_priced.json
+usage: [EXTRA=<hipcc flags of an A/B build>] python tools/sketch_priced.py <dir with the GPU outputs> \
+           > profiles/r06_sketch_priced.json
 """
 import collections
 import glob
@@ -32,7 +33,8 @@ CLASS = {
     "v_xor_b32_e32": "v_xor_b32_e32", "v_add_u32_e32": "v_add_u32_e32", "v_add3_u32": "v_add3_u32",
     "v_alignbit_b32": "v_alignbit_b32", "v_and_b32_e32": "v_and_b32_e32 (literal)", "v_bfi_b32": "v_bfi_b32",
     "v_bfrev_b32_e32": "v_bfrev_b32_e32", "v_cmp_ge_u32_e32": "v_cmp_ge_u32_e32 (vcc)",
-    "v_cmp_lt_u32_e32": "v_cmp_ge_u32_e32 (vcc)", "v_cmp_lt_u64_e32": "v_cmp_lt_u64_e32 (vcc)",
+    "v_cmp_lt_u32_e32": "v_cmp_ge_u32_e32 (vcc)", "v_cmp_le_u32_e32": "v_cmp_ge_u32_e32 (vcc)",
+    "v_add_u32_e64": "v_add_u32_e32", "v_cmp_lt_u64_e32": "v_cmp_lt_u64_e32 (vcc)",
     "v_cndmask_b32_e32": "v_cndmask_b32_e32 (vcc)", "v_lshl_add_u64": "v_lshl_add_u64",
     "v_lshlrev_b32_e32": "v_lshlrev_b32_e32", "v_lshlrev_b32_sdwa": "v_lshlrev_b32_sdwa (sgpr shift, byte select)",
     "v_or_b32_sdwa": "v_lshlrev_b32_sdwa (sgpr shift, byte select)", "v_lshlrev_b64": "v_lshlrev_b64",
@@ -50,7 +52,8 @@ def hot_mix():
         asm = os.path.join(td, "sk.s")
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only",
                         "-S", "-o", asm, os.path.join(ROOT, "drep_amd/csrc/sketch.hip"),
-                        "-I" + os.path.join(ROOT, "drep_amd/csrc")], check=True, stderr=subprocess.DEVNULL)
+                        "-I" + os.path.join(ROOT, "drep_amd/csrc")] + os.environ.get("EXTRA", "").split(),
+                       check=True, stderr=subprocess.DEVNULL)
         s = open(asm).read()
     m = re.search(r"^(_ZN7drephip\d+k_sketch_hash21ILi64ELi2E\S*):", s, re.M)
     body = s[m.start():s.index(".Lfunc_end", m.start())]
