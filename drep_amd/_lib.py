@@ -68,6 +68,7 @@ SIGNATURES = {
     "drephip_synth_device": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                        vp, vp, vp]),
     "drephip_prefilter_eval": (C.c_int, [u64p, u64p, C.c_uint64, C.c_uint64, u8p, u8p]),
+    "drephip_canon_eval": (C.c_int, [u32p, C.c_uint64, C.c_uint32, u32p, u32p]),
     "drephip_allpairs": (C.c_int, [vp, u64p, u32p, C.c_uint32, u16p, vp]),
     "drephip_allpairs_rows": (C.c_int, [vp, u64p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
     "drephip_allpairs_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]),
@@ -235,6 +236,20 @@ def prefilter_eval(q1: np.ndarray, q2: np.ndarray, T: int) -> Tuple[np.ndarray, 
     check(lib().drephip_prefilter_eval(q1 if n else z, q2 if n else z, n, int(T), ok, exact),
           "drephip_prefilter_eval")
     return ok[:n].astype(bool), exact[:n].astype(bool)
+
+
+def canon_eval(words: np.ndarray, r: int) -> Tuple[np.ndarray, np.ndarray]:
+    """drephip_canon_eval (host): (high word, tail index) of the canonical 21-mer
+    ending at base 32 + r of each row of words (n x 3 code words)."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    if words.ndim != 2 or words.shape[1] != 3:
+        raise ValueError("words must be n x 3")
+    n = len(words)
+    hi = np.zeros(max(n, 1), np.uint32)
+    tail = np.zeros(max(n, 1), np.uint32)
+    check(lib().drephip_canon_eval(words if n else np.zeros((1, 3), np.uint32), n, int(r), hi, tail),
+          "drephip_canon_eval")
+    return hi[:n], tail[:n]
 
 
 def write_mash_table(path: str, names: Sequence[str], common: np.ndarray, denom: Optional[np.ndarray], s: int,

@@ -8,7 +8,7 @@
 // fin(p) = p ^ (p >> 33),
 //     h1 = fin(p1) + fin(p2)                                  (murmur_fin)
 // and a k-mer is admitted iff h1 <= T.  The prefilter is a cheaper necessary
-// condition on (q1, q2), so the exact test runs only in the rare admit branch.
+// condition on (q1, q2), so the exact test runs only on its rare survivors.
 //
 // Identity.  Multiplication by C2 is linear mod 2^64:
 //     P = p1 + p2 = (q1 + q2) C2,
@@ -46,7 +46,15 @@ __host__ __device__ __forceinline__ uint32_t mulhi32(uint32_t a, uint32_t b) {
 // fmix64 up to its last multiply: q = ((k ^ k >> 33) C1) ^ (... >> 33); the
 // state before fmix64's final xorshift is then q C2 (fmix_mul)
 __host__ __device__ __forceinline__ uint64_t fmix64_q(uint64_t k) {
-    k ^= k >> 33; k *= kFmixC1;
+    k ^= k >> 33;
+    // x C1 = lo x lo C1 + ((lo x hi C1 + hi x lo C1) << 32) with the cross terms
+    // chained through the multiply-adds: v_mul_lo_u32 + 2 v_mad_u64_u32, where
+    // the compiler's own 64-bit multiply is v_mul_hi_u32, 2 v_mul_lo_u32, a
+    // v_mad_u64_u32 and a v_add3_u32
+    const uint32_t lo = (uint32_t)k, hi = (uint32_t)(k >> 32);
+    const uint32_t t = hi * (uint32_t)kFmixC1;
+    const uint32_t cross = (uint32_t)((uint64_t)lo * (uint32_t)(kFmixC1 >> 32) + t);
+    k = (uint64_t)lo * (uint32_t)kFmixC1 + ((uint64_t)cross << 32);
     k ^= k >> 33;
     return k;
 }

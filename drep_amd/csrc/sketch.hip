@@ -8,10 +8,10 @@
 //                     k-mers out of the code stream, hashes the canonical one
 //                     with MurmurHash3_x64_128 (seed 42, h1) using per-workgroup
 //                     LDS tables for the base-local parts, and admits it only if
-//                     h <= T[g] (per-genome candidate threshold).  Admitted
-//                     hashes are staged in LDS and, after the tile, inserted
-//                     into a per-genome open-addressing set in HBM (64-bit CAS),
-//                     so duplicates drop out at insert.
+//                     h <= T[g] (per-genome candidate threshold).  Candidates
+//                     are staged in LDS and, after the tile, tested exactly
+//                     and inserted into a per-genome open-addressing set in
+//                     HBM (64-bit CAS), so duplicates drop out at insert.
 //   k_sketch_finalize_bucket one workgroup per genome: bucket-sorts the set in
 //                     LDS and writes the s smallest.
 //   k_synth           bench input generator (not on the product path).
@@ -23,6 +23,7 @@
 // Roofline: integer VALU issue and LDS table reads (see k_sketch_hash21);
 // HBM traffic is 3 bits/base (0.375 B/base) plus the candidate sets.
 
+#include "canon.h"
 #include "ctx.h"
 #include "prefilter.h"
 #include "../../include/drephip.h"
@@ -77,10 +78,13 @@ __device__ __forceinline__ uint64_t add64(uint64_t a, uint64_t b) {   // one v_l
 // (prefilter_bound, prefilter_hi) live in prefilter.h, shared with the host
 // evaluator: the prefilter tests hi((q1 + q2) C2) + 1 <= hi(T) + 2, one 64-bit
 // add and one high-word product, a necessary condition for h1 <= T
-// Candidates are staged in an LDS buffer (wave-aggregated LDS atomic) and only
-// flushed to the per-genome set after the tile, so the hot loop issues no
-// global memory operation with a wait; a full buffer spills to the set
-// directly.
+// Candidates -- valid k-mers that pass the prefilter -- are staged in an LDS
+// buffer as (q1, q2) (wave-aggregated LDS atomic); after the tile one lane per
+// staged pair finishes the hash, runs the exact test h <= T and inserts into
+// the per-genome set.  The hot loop thus issues no global memory operation
+// with a wait, and the rare branch holds no multiply (a hit in one lane is
+// paid for by all 64).  A full buffer takes the exact test and the insert in
+// the branch.
 #ifndef DREPHIP_SK_STAGE
 #define DREPHIP_SK_STAGE 128       // ~13 admitted hashes per tile expected; overflow goes straight to the set
 #endif
@@ -89,20 +93,13 @@ constexpr uint32_t kStage = DREPHIP_SK_STAGE;
 // ------------------------------------------------------------- hash kernel
 // One workgroup of kTile / LANE lanes per 32768-base tile; lane l owns the
 // LANE window ends [tile + LANE l, tile + LANE (l + 1)).  No per-base rolling state: the
-// forward and reverse-complement k-mers are cut out of the 2-bit code stream
-// with two v_alignbit_b32 each, the canonical one is chosen on the codes, and
-// the parts of MurmurHash3_x64_128 (seed 42, h1) that depend only on a few
-// bases come from per-workgroup LDS tables.
-//
-// Streams (code word j holds bases 16j..16j+15, base i at bits 2i):
-//   NF[j] = ~F[j]: a 64-bit little-endian cut holding bases q-31..q has base q
-//     in the top bits, i.e. it is the reverse complement read MSB-first --
-//     top-aligned (bases of the k-mer in bits 22..63, junk below);
-//   R[j] = F[j] with its 16 fields reversed: a big-endian cut of R starting at
-//     base q-20 is the forward k-mer MSB-first, top-aligned the same way.
-// memcmp order of the ASCII k-mers = unsigned order of those top-aligned values
-// (A<C<G<T = 0<1<2<3; junk bits never decide: k is odd, so no k-mer equals its
-// reverse complement).
+// first 16 bases of the forward and of the reverse-complement k-mer are cut
+// out of the 2-bit code stream with one v_alignbit_b32 each, the smaller is
+// the canonical high word (the high words always differ and decide the
+// strand), the 5-base tail index is cut from the code words of the chosen
+// strand (canon.h, with the streams and the proof), and the parts of
+// MurmurHash3_x64_128 (seed 42, h1) that depend only on a few bases come from
+// per-workgroup LDS tables.
 //
 // Murmur's block words are k1 = ASCII of bases 0-7 and k2 = bases 8-15; the
 // tail k3 = bases 16-20.  A 64-bit product k * c splits as
@@ -136,6 +133,7 @@ constexpr uint32_t kStage = DREPHIP_SK_STAGE;
 // v_mad_u64_u32 and a v_lshl_add_u32.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // one LDS vector load (a struct is split)
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 struct SketchTablesQ {
     u32x4 e1[256];        // {lo(TT1), hi(TT1) + (hi(A03 c1) << 31), hi(A03 c1), 0}  by bases 0-3
     u32x4 e2[256];        // {lo(TT2), hi(TT2), hi(A03 c2), hi(A03 c2) hi(2 c1)}     by bases 8-11
@@ -189,16 +187,11 @@ __global__ __launch_bounds__(256) void k_sketch_tables(SketchTablesQ *__restrict
     for (uint32_t i = threadIdx.x; i < kTabVec; i += 256) dst[i] = src[i];
 }
 
-__device__ __forceinline__ uint32_t rev_fields16(uint32_t x) {     // reverse the 16 2-bit fields
-    const uint32_t y = __builtin_bitreverse32(x);
-    return ((y >> 1) & 0x55555555u) | ((y & 0x55555555u) << 1);
-}
-
 __device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) {   // one v_mad_u64_u32
     return (uint64_t)a * b + c;
 }
 
-// Murmur h1 of the canonical k-mer (top-aligned codes hi:lo), returned as the
+// Murmur h1 of the canonical k-mer (high word and tail offset, canon.h), returned as the
 // two fmix64 states q1, q2 before their last multiply: with p = q C2,
 // h1 = fin(p1) + fin(p2), fin(k) = k ^ (k >> 33).  C2 multiplies linearly, so
 // p1 + p2 = (q1 + q2) C2 = P, and fin leaves the high word unchanged, so hi(P)
@@ -207,7 +200,7 @@ __device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) { 
 // (both sides one past, so hi(h1) = 0 under hi(P) = 0xFFFFFFFF is kept; above
 // that hi(T) the bound is all ones and nothing is rejected): the prefilter
 // (prefilter.h: one v_lshl_add_u64, the high word of one product, a compare;
-// derivation there); the exact test runs in the rare admit branch.
+// derivation there); the exact test runs on its rare survivors, after the tile.
 // the five table entries of one k-mer
 struct MEnt { u32x4 e1; u32x2 f1; u32x4 e2; u32x2 f2; uint64_t k3; };
 // Table addresses are byte index << entry size.  The shift amounts come in
@@ -217,7 +210,7 @@ struct MEnt { u32x4 e1; u32x2 f1; u32x4 e2; u32x2 f2; uint64_t k3; };
 #ifndef DREPHIP_SK_ABLATE
 #define DREPHIP_SK_ABLATE 0
 #endif
-__device__ __forceinline__ MEnt fetch_ent(const SketchTablesQ &tb, uint32_t hi, uint32_t lo, uint32_t sh) {
+__device__ __forceinline__ MEnt fetch_ent(const SketchTablesQ &tb, uint32_t hi, uint32_t toff, uint32_t sh) {
     const char *base = (const char *)&tb;
 #if DREPHIP_SK_ABLATE
     // A/B build for the binding-resource measurement (tools/sketch_ablate.py;
@@ -230,21 +223,21 @@ __device__ __forceinline__ MEnt fetch_ent(const SketchTablesQ &tb, uint32_t hi, 
     // no tables at all: the entries are the k-mer's own words (no LDS read, no
     // address arithmetic; the hash is garbage) -- the VALU-only time of the rest
     (void)base; (void)s16; (void)s8; (void)km;
-    return MEnt{u32x4{hi, lo, hi, lo}, u32x2{lo, hi}, u32x4{lo, hi, lo, hi}, u32x2{hi, lo},
-                ((uint64_t)hi << 32) | lo};
+    return MEnt{u32x4{hi, toff, hi, toff}, u32x2{toff, hi}, u32x4{toff, hi, toff, hi}, u32x2{hi, toff},
+                ((uint64_t)hi << 32) | toff};
 #endif
     return MEnt{*(const u32x4 *)(base + (((hi >> 24) & km) << s16)),
                 *(const u32x2 *)(base + offsetof(SketchTablesQ, b1) + (((hi >> 16) & km & 0xffu) << s8)),
                 *(const u32x4 *)(base + offsetof(SketchTablesQ, e2) + (((hi >> 8) & km & 0xffu) << s16)),
                 *(const u32x2 *)(base + offsetof(SketchTablesQ, b2) + ((hi & km & 0xffu) << s8)),
-                tb.t3[(lo >> 22) & km]};
+                *(const uint64_t *)(base + offsetof(SketchTablesQ, t3) + (toff & (km << 3)))};
 #else
     const uint32_t s16 = sh & 0xffu, s8 = sh >> 8;
     return MEnt{*(const u32x4 *)(base + ((hi >> 24) << s16)),
                 *(const u32x2 *)(base + offsetof(SketchTablesQ, b1) + (((hi >> 16) & 0xffu) << s8)),
                 *(const u32x4 *)(base + offsetof(SketchTablesQ, e2) + (((hi >> 8) & 0xffu) << s16)),
                 *(const u32x2 *)(base + offsetof(SketchTablesQ, b2) + ((hi & 0xffu) << s8)),
-                tb.t3[lo >> 22]};
+                *(const uint64_t *)(base + offsetof(SketchTablesQ, t3) + toff)};
 #endif
 }
 __device__ __forceinline__ void murmur21_ent(const MEnt &E, uint32_t seed, uint64_t &q1, uint64_t &q2) {
@@ -279,9 +272,9 @@ __device__ __forceinline__ void murmur21_ent(const MEnt &E, uint32_t seed, uint6
     q1 = fmix64_q(h1);
     q2 = fmix64_q(h2);
 }
-__device__ __forceinline__ void murmur21_q(const SketchTablesQ &tb, uint32_t hi, uint32_t lo, uint32_t seed,
+__device__ __forceinline__ void murmur21_q(const SketchTablesQ &tb, uint32_t hi, uint32_t toff, uint32_t seed,
                                            uint32_t sh, uint64_t &q1, uint64_t &q2) {
-    murmur21_ent(fetch_ent(tb, hi, lo, sh), seed, q1, q2);
+    murmur21_ent(fetch_ent(tb, hi, toff, sh), seed, q1, q2);
 }
 #ifndef DREPHIP_SK_BATCH
 #define DREPHIP_SK_BATCH 2          // k-mers per admit test: 52 VGPRs (4: 58, 0.8 % slower; 8: 73, 7 waves, 2 % slower;
@@ -296,7 +289,8 @@ __device__ __forceinline__ void murmur21_q(const SketchTablesQ &tb, uint32_t hi,
 #define DREPHIP_SK_MINW 1
 #endif
 // window ends per lane: 64, i.e. 512-lane workgroups per 32768-base tile.  The
-// tables (23.5 KiB of LDS per workgroup) then serve 8 waves instead of 4, so
+// tables (20 KiB of LDS per workgroup, 22 KiB with the stage: four workgroups
+// take 88 of the CU's 160 KiB) then serve 8 waves instead of 4, so
 // LDS allows 8 waves per SIMD instead of 6: 1.3 % faster than 128 (8.24 vs
 // 8.35 ms, same box; 32 window ends per lane: 8.37 ms)
 constexpr uint32_t kHashLane = 64;
@@ -309,7 +303,7 @@ __global__ __launch_bounds__(kTile / LANE, DREPHIP_SK_MINW) void k_sketch_hash21
     constexpr uint32_t WG = kTile / LANE;
     constexpr int NCH = LANE / 16;
     __shared__ SketchTablesQ tb;
-    __shared__ uint64_t stage[kStage];
+    __shared__ u64x2 stage[kStage];                  // (q1, q2) of the prefilter's survivors
     __shared__ uint32_t nstage;
     const uint32_t t = blockIdx.x;
     const uint32_t g = tile_genome[t];
@@ -338,7 +332,7 @@ __global__ __launch_bounds__(kTile / LANE, DREPHIP_SK_MINW) void k_sketch_hash21
     auto ld = [&](int j) -> uint32_t {               // word m0 + j, m0 = the lane's first window end / 16
         return __builtin_amdgcn_raw_buffer_load_b32(crs, lane_off, (uint32_t)__builtin_amdgcn_readfirstlane(j + 2) * 4u, 0);
     };
-    // registers: F words m-2..m (complemented), R words m-2..m+1
+    // registers: F words m-2..m (complemented), R words m-2..m and, one chunk ahead, m+1
     uint32_t nf0 = ~ld(-2), nf1 = ~ld(-1), nf2 = ~ld(0);
     uint32_t r0 = rev_fields16(~nf0), r1 = rev_fields16(~nf1), r2 = rev_fields16(~nf2);
     uint32_t f3 = ld(1);                             // raw F[m+1]
@@ -360,49 +354,39 @@ __global__ __launch_bounds__(kTile / LANE, DREPHIP_SK_MINW) void k_sketch_hash21
         const uint32_t vbits = (vcur >> ((wi & 1) * 16)) & 0xffffu;
         if (wi + 1 < NCH && (wi & 1)) vcur = vw[2 + (wi >> 1)];
         vhist = (vhist >> 16) | ((uint64_t)vbits << 48);
-        // canonical k-mer (top-aligned codes) of window end q = 16m + r
-        auto canon = [&](int r) -> uint64_t {
-            uint32_t chi, clo, fhi, flo;
-            if (r == 15) { chi = nf2; clo = nf1; }
-            else {
-                chi = __builtin_amdgcn_alignbit(nf2, nf1, 2 * (r + 1));
-                clo = __builtin_amdgcn_alignbit(nf1, nf0, 2 * (r + 1));
-            }
-            if (r < 4) {                             // k-mer starts in word m-2 at field r+12
-                fhi = __builtin_amdgcn_alignbit(r0, r1, 32 - 2 * (r + 12));
-                flo = __builtin_amdgcn_alignbit(r1, r2, 32 - 2 * (r + 12));
-            } else if (r == 4) {
-                fhi = r1; flo = r2;
-            } else {                                 // starts in word m-1 at field r-4
-                fhi = __builtin_amdgcn_alignbit(r1, r2, 32 - 2 * (r - 4));
-                flo = __builtin_amdgcn_alignbit(r2, r3, 32 - 2 * (r - 4));
-            }
-            const uint64_t fw = ((uint64_t)fhi << 32) | flo;
-            const uint64_t rc = ((uint64_t)chi << 32) | clo;
-            return fw <= rc ? fw : rc;
-        };
+        // canonical k-mer of window end q = 16m + r: high word and tail offset (canon.h)
+        auto canon = [&](int r, uint32_t &hi, uint32_t &toff) { canon_cut(nf0, nf1, nf2, r0, r1, r2, r, hi, toff); };
 #pragma unroll
         for (int b0 = 0; b0 < 16; b0 += BATCH) {
             uint64_t p1[BATCH], p2[BATCH];
-            bool hit = false;
+            bool pf[BATCH], hit = false;
 #pragma unroll
             for (int b = 0; b < BATCH; b++) {
-                const uint64_t cc = canon(b0 + b);
-                murmur21_q(tb, (uint32_t)(cc >> 32), (uint32_t)cc, seed, sh, p1[b], p2[b]);
-                hit |= prefilter_hi(p1[b], p2[b]) <= Tp;
+                uint32_t chw, toff;
+                canon(b0 + b, chw, toff);
+                murmur21_q(tb, chw, toff, seed, sh, p1[b], p2[b]);
+                pf[b] = prefilter_hi(p1[b], p2[b]) <= Tp;
+                hit |= pf[b];
             }
             if (__builtin_expect(hit, 0)) {
 #pragma unroll
                 for (int b = 0; b < BATCH; b++) {
-                    const uint64_t h = murmur_fin(p1[b], p2[b]);
                     // the 21 bases ending at history bit 48 + r are all valid
                     // (per k-mer, here: a shared run mask over the whole chunk
                     // was hoisted out of this rare branch into every chunk)
                     const bool ok = (~(uint32_t)(vhist >> (28 + b0 + b)) & 0x1FFFFFu) == 0;
-                    if (h <= T && ok) {
+                    // only the k-mer's own prefilter bit and its validity here:
+                    // the survivor's (q1, q2) is staged and the exact test runs
+                    // after the tile, in as many lanes as there are survivors.
+                    // A full stage (T = kMaxThr, or a tile dense with admits)
+                    // takes the exact test and the insert in place
+                    if (pf[b] && ok) {
                         const uint32_t slot = atomicAdd(&nstage, 1u);
-                        if (slot < kStage) stage[slot] = h;
-                        else set_insert(S, mask, C, limit, h);
+                        if (slot < kStage) stage[slot] = u64x2{p1[b], p2[b]};
+                        else {
+                            const uint64_t h = murmur_fin(p1[b], p2[b]);
+                            if (h <= T) set_insert(S, mask, C, limit, h);
+                        }
                     }
                 }
             }
@@ -416,7 +400,11 @@ __global__ __launch_bounds__(kTile / LANE, DREPHIP_SK_MINW) void k_sketch_hash21
     }
     __syncthreads();
     const uint32_t n = min(nstage, kStage);
-    for (uint32_t i = threadIdx.x; i < n; i += WG) set_insert(S, mask, C, limit, stage[i]);
+    for (uint32_t i = threadIdx.x; i < n; i += WG) {
+        const u64x2 q = stage[i];
+        const uint64_t h = murmur_fin(q.x, q.y);
+        if (h <= T) set_insert(S, mask, C, limit, h);
+    }
 }
 
 // ----------------------------------------------------------------- finalize

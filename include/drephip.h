@@ -185,6 +185,16 @@ int drephip_synth_device(drephip_ctx *ctx, uint64_t seed, uint32_t g0, uint32_t 
 int drephip_prefilter_eval(const uint64_t *q1, const uint64_t *q2, uint64_t n, uint64_t T,
                            uint8_t *pass, uint8_t *exact);
 
+/* The sketch hash kernel's canonical-strand choice, evaluated on the host
+ * through the inline functions the kernel calls (drep_amd/csrc/canon.h; no
+ * context, no GPU).  words holds n triples of 2-bit code words F[m-2], F[m-1],
+ * F[m] (word j = bases 16j..16j+15, base i at bits 2i; A, C, G, T = 0..3), and
+ * r (0..15) names the window end q = 16m + r, the 21-mer of bases q-20..q.
+ * For each triple: hi[i] = bases 0-15 of the canonical k-mer (the smaller of
+ * the k-mer and its reverse complement in ASCII order), base 0 in the top two
+ * bits; tail[i] = its bases 16-20 as a 10-bit number, base 16 on top. */
+int drephip_canon_eval(const uint32_t *words, uint64_t n, uint32_t r, uint32_t *hi, uint32_t *tail);
+
 /* ---------------------------------------------------------------- dist
  * Replaces: `mash dist -p P ALL.msh ALL.msh > MASH_table.tsv`
  * (drep/d_cluster.py:569-573) for the integer part of every row: the shared-

@@ -17,14 +17,16 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "drep_amd/csrc/sketch.hip")
 HDR = os.path.join(ROOT, "drep_amd/csrc/prefilter.h")      # fmix64's tail and the prefilter (host + device)
+CANON = os.path.join(ROOT, "drep_amd/csrc/canon.h")         # the strand choice and the tail cut (host + device)
+CANON_BASE = 100000                                         # canon.h line n is carried as -(CANON_BASE + n)
 
 
 PREFILTER = "prefilter (sum, one high word, compare)"
 
 
-def func_ranges(lines, hlines):
+def func_ranges(lines, hlines, clines):
     """(first, last) source lines of the functions and regions the phases name
-    (sketch.hip; negative line numbers: prefilter.h)."""
+    (sketch.hip; negative line numbers: prefilter.h, below -CANON_BASE: canon.h)."""
     def find(pat, start=0):
         for i in range(start, len(lines)):
             if re.search(pat, lines[i]):
@@ -36,7 +38,8 @@ def func_ranges(lines, hlines):
         b = next(i + 1 for i in range(a, len(lines)) if lines[i].startswith("}"))
         return a, b
     r = {}
-    r["k-mer cut + canonical select"] = (find(r"auto canon = \["), find(r"return fw <= rc"))
+    r["k-mer cut + canonical select"] = [(find(r"auto canon = \["), find(r"auto canon = \[")),
+                                         (-(CANON_BASE + len(clines)), -(CANON_BASE + 1))]
     r["table addressing + LDS reads"] = body(r"MEnt fetch_ent\(")
     r["Murmur body (tables combined)"] = body(r"void murmur21_ent\(")
     r["Murmur helpers (rotl, *5+c, add64, mad64)"] = None   # several functions, below
@@ -56,11 +59,11 @@ def func_ranges(lines, hlines):
 
 def main():
     lines = open(SRC).read().split("\n")
-    ranges = func_ranges(lines, open(HDR).read().split("\n"))
-    hit_line = next(i + 1 for i, l in enumerate(lines) if "hit |= prefilter_hi" in l)
+    ranges = func_ranges(lines, open(HDR).read().split("\n"), open(CANON).read().split("\n"))
+    hit_lines = [i + 1 for i, l in enumerate(lines) if "pf[b] = prefilter_hi" in l or "hit |= pf[b]" in l]
 
     def phase_of(line):
-        if line == hit_line:
+        if line in hit_lines:
             return PREFILTER
         for name, rg in ranges.items():
             for a, b in (rg if isinstance(rg, list) else [rg]):
@@ -73,12 +76,14 @@ def main():
                         "--cuda-device-only", "-S", "-o", asm, SRC, "-I" + os.path.join(ROOT, "drep_amd/csrc")] +
                        os.environ.get("EXTRA", "").split(), check=True, stderr=subprocess.DEVNULL)
         s = open(asm).read()
-    fileno = hdrno = None
+    fileno = hdrno = canno = None
     for m in re.finditer(r'^\s*\.file\s+(\d+)\s+"[^"]*"\s+"([^"]*)"', s, re.M):
         if m.group(2).endswith("sketch.hip"):
             fileno = m.group(1)
         if m.group(2).endswith("prefilter.h"):
             hdrno = m.group(1)
+        if m.group(2).endswith("canon.h"):
+            canno = m.group(1)
     m = re.search(r"^(_ZN7drephip\d+k_sketch_hash21ILi64ELi2E\S*):", s, re.M)
     body = s[m.start():s.index(".Lfunc_end", m.start())]
     # blocks between labels; the hot ones hold the hash (2 k-mers' mad_u64 chains)
@@ -91,7 +96,8 @@ def main():
             continue
         lm = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
         if lm:
-            loc = int(lm.group(2)) if lm.group(1) == fileno else -int(lm.group(2)) if lm.group(1) == hdrno else 0
+            n = int(lm.group(2))
+            loc = n if lm.group(1) == fileno else -n if lm.group(1) == hdrno else -(CANON_BASE + n) if lm.group(1) == canno else 0
             continue
         if cur is None or not ln.startswith("\t") or t.startswith((".", ";")) or not t:
             continue
