@@ -84,6 +84,8 @@ SIGNATURES = {
     "drephip_allpairs_merge_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]),
     "drephip_allpairs_sparse_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64,
                                                  C.POINTER(C.c_uint64), vp]),
+    "drephip_allpairs_sparse_device_marked": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64,
+                                                        vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]),
     "drephip_allpairs_sparse": (C.c_int, [vp, u64p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64,
                                           C.POINTER(C.c_uint64)]),
     "drephip_last_sparse_stats": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -684,6 +686,19 @@ class Context:
                                                   C.byref(n), stream)
         if rc != self.ERR_NOMEM:
             check(rc, "drephip_allpairs_sparse_device")
+        return rc, n.value
+
+    def allpairs_sparse_device_marked(self, d_hashes: int, d_nhash: int, N: int, row0: int, row1: int,
+                                      d_cells: Optional[int], n_cells: int, d_records: Optional[int], n_records: int,
+                                      d_pairs: Optional[int], cap: int, stream: Optional[int] = None) -> Tuple[int, int]:
+        """drephip_allpairs_sparse_device_marked (rows [row0, row1) screened from
+        every hash part's cells and records): (return code, records the rows
+        hold); raises on every error but DREPHIP_ERR_NOMEM."""
+        n = C.c_uint64(0)
+        rc = lib().drephip_allpairs_sparse_device_marked(self._h, d_hashes, d_nhash, N, row0, row1, d_cells, n_cells,
+                                                         d_records, n_records, d_pairs, cap, C.byref(n), stream)
+        if rc != self.ERR_NOMEM:
+            check(rc, "drephip_allpairs_sparse_device_marked")
         return rc, n.value
 
     def sparse_stats(self) -> dict:

@@ -893,6 +893,30 @@ DREPHIP_EXPORT int drephip_allpairs_sparse_device(drephip_ctx *ctx, const uint64
     return rc;
 }
 
+DREPHIP_EXPORT int drephip_allpairs_sparse_device_marked(drephip_ctx *ctx, const uint64_t *d_hashes,
+                                                         const uint32_t *d_nhash, uint32_t N, uint32_t row0,
+                                                         uint32_t row1, const uint32_t *d_cells, uint64_t n_cells,
+                                                         const uint32_t *d_records, uint64_t n_records,
+                                                         uint32_t *d_pairs, uint64_t cap, uint64_t *n_pairs,
+                                                         void *stream) {
+    GUARD_CTX(ctx);
+    if (!d_hashes || !d_nhash || !n_pairs || (cap && !d_pairs) || (n_cells && !d_cells) || (n_records && !d_records)) {
+        set_error("null argument");
+        return DREPHIP_ERR_ARG;
+    }
+    *n_pairs = 0;
+    if ((uint64_t)N * ctx->s >= (1ull << 32)) { set_error("the screen needs N x s < 2^32"); return DREPHIP_ERR_UNSUPPORTED; }
+    if (ctx->ap_path == DREPHIP_AP_MERGE) { set_error("marks need the table or band path"); return DREPHIP_ERR_ARG; }
+    timing_begin(ctx);
+    ctx->ext = ExtMarks{true, (const uint4 *)d_cells, n_cells, (const uint4 *)d_records, n_records};
+    int rc = allpairs_sparse_impl(ctx, d_hashes, d_nhash, N, row0, row1, (uint4 *)d_pairs, cap, n_pairs,
+                                  pick_stream(ctx, stream));
+    ctx->ext = ExtMarks{};
+    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
+    timing_collect(ctx);
+    return rc;
+}
+
 DREPHIP_EXPORT int drephip_allpairs_sparse(drephip_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash, uint32_t N,
                                            uint32_t row0, uint32_t row1, uint32_t *pairs, uint64_t cap,
                                            uint64_t *n_pairs) {

@@ -107,8 +107,9 @@ struct PartResult {
     uint32_t nrec = 0;
     uint64_t entries = 0, runs = 0, checks = 0;
 };
-// Marks handed to the next all-pairs call (drephip_allpairs_device_marked):
-// the parts' cell words and records; the call screens its rows from them.
+// Marks handed to the next all-pairs call (drephip_allpairs_device_marked,
+// drephip_allpairs_sparse_device_marked): the parts' cell words and records;
+// the call screens its rows from them.
 struct ExtMarks {
     bool active = false;
     const uint4 *cells = nullptr;
@@ -141,7 +142,7 @@ struct drephip_ctx {
     ScreenResult last_screen; // the last all-pairs call's screen (stats; pointers into scratch)
     SparseStats sparse;       // the last sparse all-pairs call
     PartResult part;          // the last sharded-screen part (drephip_screen_part)
-    ExtMarks ext;             // marks for the current drephip_allpairs_device_marked call
+    ExtMarks ext;             // marks for the current drephip_allpairs_[sparse_]device_marked call
     int link_path = 0;        // DREPHIP_LINK_PATH_*: 0 auto (sparse when it applies, else dense)
     uint32_t band_cap = 1024; // elements per row per band of the banded all-pairs kernel (clamped to its LDS budget)
     uint32_t band_round = 0;  // elements per row per value round of the band kernel (0: no rounds; A/B)
@@ -274,7 +275,8 @@ constexpr uint32_t kListCols = 512;             // screened columns per whole-ro
 // The sparse all-pairs call (sparse.h; driver in screen.hip): rows [row0, row1)
 // as records {i, j, common, denom} of the pairs with common > 0 only, no
 // condensed vector.  *n_pairs = the records the rows hold (> cap: the list is
-// incomplete, nothing is stored past cap).  Blocking.
+// incomplete, nothing is stored past cap).  Blocking.  With ctx->ext active
+// the rows are screened from the given marks instead of a grouping of their own.
 struct SparseOut;
 int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
                          uint32_t row0, uint32_t row1, uint4 *d_pairs, uint64_t cap, uint64_t *n_pairs,

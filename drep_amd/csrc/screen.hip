@@ -484,7 +484,8 @@ __global__ __launch_bounds__(kScWG) void k_screen_map2(const uint4 *__restrict__
 // {row tile T (rows [T R, (T + 1) R) from row 0), word w (columns 32 w ..
 // 32 w + 31), bits, 0} -- ~1 record per marked cell word, against N^2 / (32 R)
 // words of the whole bitmap (312 MB per part at 10^5 genomes).  Counted per
-// chunk, scanned, written in order.
+// chunk, scanned, written in order.  The bitmap is walked in blocks of row
+// tiles (screen_part_impl): bm holds the tiles from t0 on.
 __global__ __launch_bounds__(kScWG) void k_cells_count(const uint32_t *__restrict__ bm, uint64_t nwords, uint32_t chunk,
                                                        uint32_t *__restrict__ bcount) {
     __shared__ uint32_t red[kScWG / 64];
@@ -503,7 +504,7 @@ __global__ __launch_bounds__(kScWG) void k_cells_count(const uint32_t *__restric
 }
 __global__ __launch_bounds__(kScWG) void k_cells_write(const uint32_t *__restrict__ bm, uint64_t nwords, uint32_t chunk,
                                                        const uint32_t *__restrict__ boff, uint32_t NW,
-                                                       uint4 *__restrict__ cells) {
+                                                       uint32_t t0, uint4 *__restrict__ cells) {
     __shared__ uint32_t wsum[kScWG / 64];
     const uint64_t i0 = (uint64_t)blockIdx.x * chunk, i1 = min(i0 + chunk, nwords);
     uint32_t o = boff[blockIdx.x];
@@ -512,7 +513,7 @@ __global__ __launch_bounds__(kScWG) void k_cells_write(const uint32_t *__restric
         const uint32_t v = i < i1 ? bm[i] : 0u;
         uint32_t tot;
         const uint32_t q = o + block_exclusive_count(v != 0, wsum, &tot);
-        if (v) cells[q] = make_uint4((uint32_t)(i / NW), (uint32_t)(i % NW), v, 0u);
+        if (v) cells[q] = make_uint4(t0 + (uint32_t)(i / NW), (uint32_t)(i % NW), v, 0u);
         o += tot;
     }
 }
@@ -1390,7 +1391,8 @@ int screen_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nh
 // ------------------------------------------------------- the sharded screen
 // Part `part` of `nparts` hash ranges (one per rank of a sharded job): its
 // entries grouped, its runs of >= 3 marked into a bitmap of row tiles of R
-// rows counted from row 0 -- every row, not only this rank's -- sent out as
+// rows counted from row 0 -- every row, not only this rank's, a block of row
+// tiles at a time so that the bitmap stays inside a budget -- sent out as
 // its nonzero words (cell records), and its runs of two listed as records.
 // The caller routes every part's cells and records to the ranks owning their
 // rows (drephip_screen_part_copy), and each rank finishes its rows from them
@@ -1412,43 +1414,79 @@ int screen_part_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t 
     ScreenFront F;
     if ((rc = screen_front(ctx, d_hashes, d_nhash, N, part, nparts, st, prof, &F))) return rc;
     const uint32_t NW = (N + 31) / 32, ntg = (N + R - 1) / R, rshift = tile_shift(R);
+    // Row tiles per block of the bitmap: an eighth of the free HBM, as the
+    // sparse call's row blocks take (DREPHIP_SCREEN_PART_BLOCK_TILES
+    // overrides, tests).  One block is the whole bitmap, ntg x N / 32 words.
+    uint64_t bt = 0;
+    if (const char *e = getenv("DREPHIP_SCREEN_PART_BLOCK_TILES")) bt = strtoull(e, nullptr, 10);
+    if (!bt) {
+        size_t fr = 0, tot = 0;
+        HIPC(hipMemGetInfo(&fr, &tot));
+        bt = std::max<uint64_t>(fr / 8, 1ull << 20) / ((uint64_t)NW * 4);
+    }
+    bt = std::min<uint64_t>(std::max<uint64_t>(bt, 1), ntg);
     uint32_t *d_gbm, *d_nrec;
     uint4 *d_rec;
-    const uint64_t gwords = (uint64_t)ntg * NW;
-    if ((rc = scratch(ctx, "sc_part_bitmap", gwords * 4, (void **)&d_gbm))) return rc;
+    const uint64_t bwords = bt * NW;
+    if ((rc = scratch(ctx, "sc_part_bitmap", bwords * 4, (void **)&d_gbm))) return rc;
     if ((rc = scratch(ctx, "sc_part_nrec", 8, (void **)&d_nrec))) return rc;
     if ((rc = scratch(ctx, "sc_part_rec", (uint64_t)std::max<uint32_t>(F.n2, 1) * 16, (void **)&d_rec))) return rc;
-    HIPC(hipMemsetAsync(d_gbm, 0, gwords * 4, st));
     HIPC(hipMemsetAsync(d_nrec, 0, 4, st));
-    if (F.M >= 2) {
-        if ((rc = screen_mark_runs(ctx, F, d_hashes, N, 0, N, rshift, NW, d_gbm, nullptr, nullptr, st, prof))) return rc;
-        if (F.n2) {
-            const uint32_t g2 = std::max(1u, std::min(8192u, (F.n2 + kScWG - 1) / kScWG));
-            hipLaunchKernelGGL(k_screen_emit2, dim3(g2), dim3(kScWG), 0, st, F.v_out, d_hashes, s, F.vmask, F.pairs, F.n2,
-                               d_rec, d_nrec);
-        }
-        prof.mark("mark", st);
+    if (F.M >= 2 && F.n2) {
+        const uint32_t g2 = std::max(1u, std::min(8192u, (F.n2 + kScWG - 1) / kScWG));
+        hipLaunchKernelGGL(k_screen_emit2, dim3(g2), dim3(kScWG), 0, st, F.v_out, d_hashes, s, F.vmask, F.pairs, F.n2,
+                           d_rec, d_nrec);
     }
-    // the marks as cell words (nonzero words of the bitmap)
-    const uint32_t cchunk = (uint32_t)std::max<uint64_t>(8192, (gwords + 8191) / 8192);
-    const uint32_t ncb = (uint32_t)((gwords + cchunk - 1) / cchunk);
-    uint32_t *ccnt, *coff;
-    if ((rc = scratch(ctx, "sc_cells_cnt", (ncb + 1) * 4ull, (void **)&ccnt))) return rc;
-    if ((rc = scratch(ctx, "sc_cells_off", (ncb + 1) * 4ull, (void **)&coff))) return rc;
-    HIPC(hipMemsetAsync(ccnt + ncb, 0, 4, st));
-    hipLaunchKernelGGL(k_cells_count, dim3(ncb), dim3(kScWG), 0, st, d_gbm, gwords, cchunk, ccnt);
-    if ((rc = hip_scan(ctx, "sc_scan_tmp6", ccnt, coff, ncb + 1, st))) return rc;
     uint64_t *h_tot;
     if ((rc = pinned_host(ctx, "sc_tot", 64, (void **)&h_tot))) return rc;
-    HIPC(hipMemcpyAsync(h_tot, d_nrec, 4, hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync((uint32_t *)h_tot + 1, coff + ncb, 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(h_tot + 1, d_nrec, 4, hipMemcpyDeviceToHost, st));
+    // the marks as cell words (nonzero words of the bitmap), block after block
+    // in ascending tile order: the whole bitmap's order.  The list grows
+    // between two buffers (a scratch buffer that grows loses its contents).
+    const uint32_t cchunk = (uint32_t)std::max<uint64_t>(8192, (bwords + 8191) / 8192);
+    const uint32_t ncb_max = (uint32_t)((bwords + cchunk - 1) / cchunk);
+    uint32_t *ccnt, *coff;
+    if ((rc = scratch(ctx, "sc_cells_cnt", (ncb_max + 1) * 4ull, (void **)&ccnt))) return rc;
+    if ((rc = scratch(ctx, "sc_cells_off", (ncb_max + 1) * 4ull, (void **)&coff))) return rc;
+    static const char *const kCellBufs[2] = {"sc_part_cells", "sc_part_cells_b"};
+    int cur = 0;
+    uint4 *d_cells = nullptr;
+    uint64_t ccap = 0, ncells64 = 0;
+    for (uint32_t t0 = 0; t0 < ntg; t0 += (uint32_t)bt) {
+        const uint32_t t1 = (uint32_t)std::min<uint64_t>(ntg, t0 + bt);
+        const uint64_t gwords = (uint64_t)(t1 - t0) * NW;
+        const uint32_t r0 = t0 * R, r1 = (uint32_t)std::min<uint64_t>(N, (uint64_t)t1 * R);
+        HIPC(hipMemsetAsync(d_gbm, 0, gwords * 4, st));
+        if (F.M >= 2) {
+            if ((rc = screen_mark_runs(ctx, F, d_hashes, N, r0, r1, rshift, NW, d_gbm, nullptr, nullptr, st, prof))) return rc;
+            prof.mark("mark", st);
+        }
+        const uint32_t ncb = (uint32_t)((gwords + cchunk - 1) / cchunk);
+        HIPC(hipMemsetAsync(ccnt + ncb, 0, 4, st));
+        hipLaunchKernelGGL(k_cells_count, dim3(ncb), dim3(kScWG), 0, st, d_gbm, gwords, cchunk, ccnt);
+        if ((rc = hip_scan(ctx, "sc_scan_tmp6", ccnt, coff, ncb + 1, st))) return rc;
+        HIPC(hipMemcpyAsync(h_tot, coff + ncb, 4, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        const uint32_t nb = ((const uint32_t *)h_tot)[0];
+        if (ncells64 + nb > 0xFFFFFFFFull) { set_error("the screen part holds 2^32 cell words or more"); return DREPHIP_ERR_UNSUPPORTED; }
+        if (!d_cells || ncells64 + nb > ccap) {
+            // (the first block sizes the list exactly: one block, one buffer)
+            const uint64_t want = d_cells ? std::max(ncells64 + nb, 2 * ccap) : std::max<uint64_t>(nb, 1);
+            uint4 *d_new;
+            const int nxt = d_cells ? cur ^ 1 : cur;
+            if ((rc = scratch(ctx, kCellBufs[nxt], want * 16, (void **)&d_new))) return rc;
+            if (ncells64) HIPC(hipMemcpyAsync(d_new, d_cells, ncells64 * 16, hipMemcpyDeviceToDevice, st));
+            d_cells = d_new;
+            ccap = want;
+            cur = nxt;
+        }
+        hipLaunchKernelGGL(k_cells_write, dim3(ncb), dim3(kScWG), 0, st, d_gbm, gwords, cchunk, coff, NW, t0,
+                           d_cells + ncells64);
+        HIPC(hipGetLastError());
+        ncells64 += nb;
+    }
     HIPC(hipStreamSynchronize(st));
-    const uint32_t ncells = ((const uint32_t *)h_tot)[1];
-    uint4 *d_cells;
-    if ((rc = scratch(ctx, "sc_part_cells", (uint64_t)std::max<uint32_t>(ncells, 1) * 16, (void **)&d_cells))) return rc;
-    hipLaunchKernelGGL(k_cells_write, dim3(ncb), dim3(kScWG), 0, st, d_gbm, gwords, cchunk, coff, NW, d_cells);
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(st));
+    const uint32_t ncells = (uint32_t)ncells64;
     prof.mark("cells", st);
     timing_mark(ctx, 4, st, false);
     ctx->part.valid = true;
@@ -1457,7 +1495,7 @@ int screen_part_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t 
     ctx->part.cells = d_cells;
     ctx->part.ncells = ncells;
     ctx->part.rec = d_rec;
-    ctx->part.nrec = ((const uint32_t *)h_tot)[0];
+    ctx->part.nrec = ((const uint32_t *)h_tot)[2];                   // the records' count (h_tot + 1, above)
     ctx->part.entries = F.M;
     ctx->part.runs = (uint64_t)F.n2 + F.nruns;
     ctx->part.checks = F.E;
@@ -1555,6 +1593,11 @@ int screen_fill_impl(drephip_ctx *ctx, const uint32_t *d_nhash, uint32_t N, uint
 // every pair has one writer: k_screen_simple<true> for a pair held by one run
 // of two in an unmarked cell, the SPARSE LIST kernel for every pair of a
 // marked cell.
+//
+// Marked form (drephip_allpairs_sparse_device_marked, a rank of a sharded
+// job): no grouping here; each block takes its marks from every hash part's
+// cells and records (sparse_marked_block), the fallback's dense call screens
+// its rows from the same marks.
 //
 // Fallback (every other plan: band path, screen off or dense verdict, N x s >=
 // 2^32, the literal merge; and the rest of a call once a block's pair map or
@@ -1678,6 +1721,69 @@ static int sparse_direct_block(drephip_ctx *ctx, const ScreenFront &F, const uin
     return DREPHIP_OK;
 }
 
+// one block of the direct path of a marked call (ctx->ext: every hash part's
+// cells and records): the cells clipped to the block's rows, the pair map from
+// the records of these rows, then as sparse_direct_block.  A part's tile that
+// straddles the block's first or last row gives its whole word to the block's
+// tiles it touches -- a superset, which costs LIST work only: the LIST kernel
+// appends the rows [row0, row1) of a marked cell and nothing else, and phase 1
+// skips every pair of a marked cell.  A pair held by runs of two in two parts
+// arrives as two records of one key (pcnt 2: the LIST kernel's); one held by a
+// run of two here and a longer run there finds its cell marked by the cells.
+static int sparse_marked_block(drephip_ctx *ctx, const uint32_t *d_nhash, uint32_t N, uint32_t row0, uint32_t row1,
+                               uint32_t R, const SparseOut &out, hipStream_t st, ScreenProf &prof, ScreenResult *res,
+                               unsigned long long **d_nsimple_out) {
+    *res = ScreenResult{};
+    *d_nsimple_out = nullptr;
+    const ExtMarks &ext = ctx->ext;
+    const uint32_t s = ctx->s;
+    const uint32_t ntiles = (row1 - row0 + R - 1) / R, NW = (N + 31) / 32, rshift = tile_shift(R);
+    int rc;
+    uint32_t *d_bm;
+    unsigned long long *pkey = nullptr, *d_nsimple;
+    uint32_t *pcnt = nullptr, *ppos = nullptr;
+    uint64_t pcap, nown = 0;
+    if ((rc = scratch(ctx, "sc_bitmap", (uint64_t)ntiles * NW * 4, (void **)&d_bm))) return rc;
+    if ((rc = scratch(ctx, "sc_nsimple", 8, (void **)&d_nsimple))) return rc;
+    if (ext.nrec) {
+        uint64_t *h_tot;
+        if ((rc = pinned_host(ctx, "sc_tot", 64, (void **)&h_tot))) return rc;
+        HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
+        const uint32_t gc = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1024, (ext.nrec + kScWG - 1) / kScWG));
+        hipLaunchKernelGGL(k_rec_count, dim3(gc), dim3(kScWG), 0, st, ext.rec, ext.nrec, row0, row1, d_nsimple);
+        HIPC(hipMemcpyAsync(h_tot, d_nsimple, 8, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        nown = h_tot[0];
+    }
+    if ((rc = screen_pair_map(ctx, nown, st, &pcap, &pkey, &pcnt, &ppos))) return rc;
+    if (pcap > kMaxPairMap) return DREPHIP_OK;
+    HIPC(hipMemsetAsync(d_bm, 0, (uint64_t)ntiles * NW * 4, st));
+    HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
+    if (ext.ncells) {
+        const uint32_t gc = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, (ext.ncells + kScWG - 1) / kScWG));
+        hipLaunchKernelGGL(k_cells_scatter, dim3(gc), dim3(kScWG), 0, st, ext.cells, ext.ncells, row0, row1, rshift, NW, d_bm);
+    }
+    prof.mark("cells", st);
+    const uint32_t gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (pcap + kScWG - 1) / kScWG));
+    if (nown) {
+        const uint32_t g2 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(8192, (ext.nrec + kScWG - 1) / kScWG));
+        hipLaunchKernelGGL(k_screen_map2, dim3(g2), dim3(kScWG), 0, st, ext.rec, ext.nrec, row0, row1, pkey, pcnt, ppos,
+                           (uint32_t)(pcap - 1));
+        hipLaunchKernelGGL(k_screen_simple<true>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
+                           row0, rshift, NW, 0ull, d_bm, nullptr, nullptr, d_nsimple, out, 0);
+    }
+    prof.mark("pairs", st);
+    HIPC(hipGetLastError());
+    if ((rc = screen_lists(ctx, d_bm, ntiles, NW, kListCols, row0, R, d_nsimple, st, prof, res))) return rc;
+    if (!res->use) return DREPHIP_OK;
+    if (nown)
+        hipLaunchKernelGGL(k_screen_simple<true>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
+                           row0, rshift, NW, 0ull, d_bm, nullptr, nullptr, d_nsimple, out, 1);
+    HIPC(hipGetLastError());
+    *d_nsimple_out = d_nsimple;
+    return DREPHIP_OK;
+}
+
 int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
                          uint32_t row0, uint32_t row1, uint4 *d_pairs, uint64_t cap, uint64_t *n_pairs,
                          hipStream_t st) {
@@ -1704,10 +1810,15 @@ int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
     uint64_t total = 0;
     uint32_t b0 = row0;
 
-    bool direct = path == DREPHIP_AP_TABLE && !ctx->ext.active && screen_applies(ctx, N);
+    // marks given (drephip_allpairs_sparse_device_marked): the caller has
+    // grouped the entries and taken the screen's verdict; the fallback's dense
+    // call below screens its rows from the same marks (ctx->ext)
+    const bool marked = ctx->ext.active;
+    bool direct = path == DREPHIP_AP_TABLE && (marked || screen_applies(ctx, N));
     ScreenProf prof;
     ScreenFront F;
-    if (direct) {
+    if (marked) prof.mark("start", st);
+    if (direct && !marked) {
         prof.mark("start", st);
         timing_mark(ctx, 4, st, true);
         rc = screen_front(ctx, d_hashes, d_nhash, N, 0, 1, st, prof, &F);
@@ -1736,7 +1847,8 @@ int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
             ScreenResult res;
             unsigned long long *d_nsimple = nullptr;
             timing_mark(ctx, 4, st, true);
-            rc = sparse_direct_block(ctx, F, d_hashes, d_nhash, N, b0, b1, R, out, st, prof, &res, &d_nsimple);
+            rc = marked ? sparse_marked_block(ctx, d_nhash, N, b0, b1, R, out, st, prof, &res, &d_nsimple)
+                        : sparse_direct_block(ctx, F, d_hashes, d_nhash, N, b0, b1, R, out, st, prof, &res, &d_nsimple);
             timing_mark(ctx, 4, st, false);
             if (rc) return rc;
             if (!res.use) break;                      // this block and the rest: the fallback
@@ -1753,6 +1865,12 @@ int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
             acc.simple += d_nsimple ? h_tot[1] : 0;
             ctx->sparse.blocks++;
             b0 = b1;
+        }
+        if (marked && acc.use && ctx->part.valid && ctx->part.N == N) {
+            // this rank's own part (the entries it grouped), as screen_marked_impl reports
+            acc.entries = ctx->part.entries;
+            acc.runs = ctx->part.runs;
+            acc.checks = ctx->part.checks;
         }
         ctx->sparse.direct = total;
         ctx->last_screen = acc;                       // (stats only: no list pointers)

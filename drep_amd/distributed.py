@@ -24,6 +24,14 @@ cluster_mash_database 598-630 -> store_special('primary_linkage')).  Here:
                  formats of drep_amd.store (condensed counts + the reference's
                  primary_linkage pickle).
 
+With --sparse (run_sharded_sparse) stages 3-5 never hold anything of size
+N^2: each rank lists the pairs of its rows that share a hash
+(allpairs_sparse_rows_sharded: the sharded screen's marks, then
+drephip_allpairs_sparse_device_marked), the root gathers the lists
+(parallel.gather_pair_lists) and clusters from them (SparseMash ->
+d_cluster.cluster_mash_sparse, the host's drephip_linkage_sparse): no
+condensed vector, no n x n linkage matrix.
+
 The stage functions are parameters of run_sharded so the plumbing (shards,
 gather order, uneven segments, root assembly) is the same code whether the
 per-rank compute is the HIP library (product) or a CPU stand-in (the gloo
@@ -39,8 +47,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .parallel import (balanced_shards, cond_start, gather_sketches, genome_shard, row_partition, segment_size,
-                       shard_layout)
+from .parallel import (balanced_shards, cond_start, gather_pair_lists, gather_sketches, genome_shard, row_partition,
+                       segment_size, shard_layout)
 
 
 @dataclass
@@ -213,6 +221,66 @@ def run_sharded(N: int, names: Sequence[str], s: int, sketch_fn: SketchFn, allpa
         Cdb = _primary_cdb(fcl, sorted(names))
         res.update(Cdb=Cdb, linkage=Z, common=full_c, denom=full_d, hashes=H, nhash=NH,
                    arguments={"linkage_method": method, "linkage_cutoff": cutoff, "comparison_algorithm": "MASH"})
+    return res
+
+
+SparseFn = Callable[..., Tuple["object", int]]            # fn(H, NH, plan) -> (records [>= n, 4] int32 by (i, j), n)
+
+
+def run_sharded_sparse(N: int, names: Sequence[str], s: int, sketch_fn: SketchFn, sparse_fn: SparseFn,
+                       method: str = "average", P_ani: float = 0.9, root: int = 0,
+                       sync: Optional[Callable[[], None]] = None, weights: Optional[Sequence[float]] = None) -> Dict:
+    """run_sharded without anything of size N^2: each rank lists the pairs of
+    its rows that share a hash (sparse_fn: records {i, j, common, denom} sorted
+    by (i, j)), the root gathers the lists and clusters from them
+    (d_cluster.cluster_mash_sparse: the same Z and Cdb as the dense job, bit
+    for bit).  No condensed tensor, no linkage matrix.
+
+    Returns, on the root, {'Cdb', 'linkage', 'arguments', 'pairs' (int32
+    [n, 4], sorted by (i, j)), 'hashes', 'nhash', 'times', 'plan', 'rank_pairs'};
+    on the other ranks {'times', 'plan', 'rank_pairs'}."""
+    import torch
+    import torch.distributed as dist
+    from .d_cluster import SparseMash, cluster_mash_sparse
+    world, rank = dist.get_world_size(), dist.get_rank()
+    p = plan(N, world, rank, weights)
+    sync = sync or (lambda: None)
+    times: Dict[str, float] = {}
+
+    def stage(name, fn):
+        sync()
+        dist.barrier()
+        t0 = time.perf_counter()
+        out = fn()
+        sync()
+        dist.barrier()
+        times[name] = time.perf_counter() - t0
+        return out
+
+    loc_h, loc_n = stage("sketch_s", lambda: sketch_fn(p))
+    H, NH = stage("allgather_s", lambda: gather_sketches(loc_h, loc_n))
+    if p.pos is None:
+        H, NH = H[:N], NH[:N]
+    else:                                    # balanced shards: gathered rows back to genome order
+        idx = torch.from_numpy(p.pos).to(H.device)
+        H, NH = H[idx].contiguous(), NH[idx].contiguous()
+    rec, n = stage("allpairs_s", lambda: sparse_fn(H, NH, p))
+    full = stage("gather_pairs_s", lambda: gather_pair_lists(rec, n, root))
+    res: Dict = {"times": times, "plan": p, "rank_pairs": int(n)}
+    if rank == root:
+        t0 = time.perf_counter()
+        pairs = full.cpu().numpy().view(np.uint32)
+        # the lists are owned by ascending row ranges and each is sorted: so is
+        # their concatenation
+        key = pairs[:, 0].astype(np.int64) * N + pairs[:, 1].astype(np.int64)
+        if len(key) > 1 and not (key[1:] > key[:-1]).all():
+            raise RuntimeError("the gathered pair list is not in (i, j) order")
+        sm = SparseMash(list(names), list(names), np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1]),
+                        pairs[:, 2].astype(np.uint16), pairs[:, 3].astype(np.uint16),
+                        NH.cpu().numpy().view(np.uint32), np.zeros(N, np.uint64), s)
+        Cdb, (Z, _, arguments) = cluster_mash_sparse(sm, clusterAlg=method, P_ani=P_ani)
+        times["linkage_s"] = time.perf_counter() - t0
+        res.update(Cdb=Cdb, linkage=Z, pairs=full, sparse=sm, hashes=H, nhash=NH, arguments=arguments)
     return res
 
 
@@ -444,6 +512,77 @@ def hip_allpairs(ctx, stream: int, device):
     return fn
 
 
+def allpairs_sparse_rows_sharded(ctx, H, NH, N: int, r0: int, r1: int, stream: int, device):
+    """Rows [r0, r1) as a pair list (every rank calls it: collective when the
+    sharded screen applies).  The screen is sharded as in allpairs_rows_sharded
+    -- drephip_screen_part, the copy, parallel.exchange_screen_parts -- and the
+    rank then lists its rows from the marks it received
+    (drephip_allpairs_sparse_device_marked); a dense set takes
+    drephip_allpairs_sparse_device with the screen off, as does a job the
+    sharded screen does not apply to (one rank, DREPHIP_SCREEN_SHARD=0, no
+    screen for this N) with the context's own screen mode.  The first buffer
+    is a guess (8 records per row + 4096), with one retry at the size the
+    library reports.  Returns (the records {i, j, common, denom} as an int32
+    [n, 4] tensor sorted by (i, j), n)."""
+    import torch
+    import torch.distributed as dist
+    from .parallel import exchange_screen_parts
+    hp, np_ = H.data_ptr(), NH.data_ptr()
+    call = None
+    restore = None
+    if sharded_screen_applies(ctx, N):
+        world = dist.get_world_size()
+        checks, ncells, nrec = ctx.screen_part(hp, np_, N, dist.get_rank(), world, stream)
+        cells = torch.empty((max(ncells, 1), 4), dtype=torch.int32, device=device)
+        rec = torch.empty((max(nrec, 1), 4), dtype=torch.int32, device=device)
+        ctx.screen_part_copy(cells.data_ptr(), rec.data_ptr(), stream)
+        starts = [a for a, _ in row_partition(N, world)]
+        cells, recs, total = exchange_screen_parts(cells, ncells, rec, nrec, checks, starts, ctx.screen_geometry())
+        if ctx.screen_worth(N, total)[1]:
+            def call(ptr, cap):
+                return ctx.allpairs_sparse_device_marked(hp, np_, N, r0, r1, cells.data_ptr() if len(cells) else None,
+                                                         len(cells), recs.data_ptr() if len(recs) else None, len(recs),
+                                                         ptr, cap, stream)
+        else:                                 # a dense set: the dense plan, compacted
+            restore = ctx.allpairs_screen
+            ctx.set_allpairs_screen(ctx.SCREEN_OFF)
+    if call is None:
+        def call(ptr, cap):
+            return ctx.allpairs_sparse_device(hp, np_, N, r0, r1, ptr, cap, stream)
+    try:
+        cap = 8 * max(r1 - r0, 0) + 4096
+        buf = torch.empty((cap, 4), dtype=torch.int32, device=device)
+        rc, n = call(buf.data_ptr(), cap)
+        if rc == ctx.ERR_NOMEM:
+            del buf
+            cap = n
+            buf = torch.empty((cap, 4), dtype=torch.int32, device=device)
+            rc, n = call(buf.data_ptr(), cap)
+            if rc:
+                raise RuntimeError("the pair list still does not fit after the retry (%d records, room for %d)" % (n, cap))
+    finally:
+        if restore is not None:
+            ctx.set_allpairs_screen(restore)
+    rec = buf[:n]
+    if n > 1:
+        order = torch.argsort(rec[:, 0].to(torch.int64) * N + rec[:, 1].to(torch.int64))
+        rec = rec[order].contiguous()
+    return rec, n
+
+
+def hip_allpairs_sparse(ctx, stream: int, device, stats: Optional[Dict] = None):
+    """Stage 3 of the sparse job: this rank's rows as a pair list
+    (allpairs_sparse_rows_sharded).  `stats` receives the call's sparse_stats
+    and screen_stats."""
+    def fn(H, NH, p: ShardPlan):
+        rec, n = allpairs_sparse_rows_sharded(ctx, H, NH, p.N, p.r0, p.r1, stream, device)
+        if stats is not None:
+            stats["sparse_stats"] = ctx.sparse_stats()
+            stats["screen_stats"] = ctx.screen_stats()
+        return rec, n
+    return fn
+
+
 def hip_linkage(ctx, names: Sequence[str], stream: int):
     """Stage 5: drephip_linkage_counts_device on the root GPU, rows in
     sorted-name order (the pivot's order, d_cluster.py:620)."""
@@ -531,6 +670,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--group-size", type=int, default=1000, help="genomes per sketch chunk folder (dRep groupSize)")
     ap.add_argument("--processors", type=int, default=int(os.environ.get("OMP_NUM_THREADS", "0") or 0),
                     help="host threads for FASTA ingest per rank (0 = all)")
+    ap.add_argument("--sparse", action="store_true",
+                    help="list only the pairs that share a hash: no condensed vector, no n x n linkage matrix on any rank")
     a = ap.parse_args(argv)
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -564,6 +705,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         lengths = np.full(N, a.genome_bp, np.uint64)
         sketch_fn = hip_synth_sketcher(ctx, a.genome_bp, a.family_size, a.seed, stream, dev)
         weights = None                                   # one length: contiguous equal shards
+    if a.sparse:
+        rc = _main_sparse(a, ctx, N, names, locations, lengths, sketch_fn, weights, stream, dev, rank, world, backend,
+                          from_files, len(cached) if from_files else 0)
+        ctx.close()
+        dist.destroy_process_group()
+        return rc
     # the root's n x n linkage matrix (80 GB at 10^5: ~2 s of hipMalloc) is
     # allocated by a separate context on a helper thread while the sketch and
     # all-pairs stages run, so the serial clustering tail does not pay for it
@@ -617,6 +764,52 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         link_ctx.close()
     ctx.close()
     dist.destroy_process_group()
+    return 0
+
+
+def _main_sparse(a, ctx, N, names, locations, lengths, sketch_fn, weights, stream, dev, rank, world, backend,
+                 from_files, ncached) -> int:
+    """main() with --sparse: run_sharded_sparse, the per-rank figures gathered
+    to the root, the results stored in the sparse work-directory formats."""
+    import torch
+    import torch.distributed as dist
+    stats: Dict = {}
+    torch.cuda.reset_peak_memory_stats(dev)
+    res = run_sharded_sparse(N, names, a.sketch, sketch_fn, hip_allpairs_sparse(ctx, stream, dev, stats), a.method,
+                             a.P_ani, sync=lambda: torch.cuda.synchronize(dev), weights=weights)
+    sp = stats.get("sparse_stats", {"blocks": 0, "direct": 0, "fallback": 0, "scratch_bytes": 0})
+    mine = {"rank": rank, "rows": [res["plan"].r0, res["plan"].r1], "pairs": res["rank_pairs"], "sparse_stats": sp,
+            "screen_used": bool(stats.get("screen_stats", {}).get("used", False)),
+            # torch's allocations (sketches, marks, the list) plus the library's own scratch
+            "peak_device_bytes": int(torch.cuda.max_memory_allocated(dev)) + int(sp["scratch_bytes"])}
+    ranks = [None] * world
+    dist.all_gather_object(ranks, mine)
+    if from_files and world > 1:
+        allv = [None] * world
+        dist.all_gather_object(allv, lengths)
+        lengths = np.maximum.reduce(allv)
+    if rank == 0:
+        out = {"job": "configs[3]-style sharded Mash step + primary clustering", "genomes": N,
+               "input": ("files (%d cached sketches)" % ncached) if from_files else "synthetic",
+               "genome_bp": None if from_files else a.genome_bp, "sketch": a.sketch, "n_gpus": world,
+               "backend": backend, "method": a.method, "P_ani": a.P_ani, "times": res["times"],
+               "pairs": N * (N - 1) // 2, "sparse": True, "pairs_listed": int(res["pairs"].shape[0]),
+               "ranks": ranks, "primary_clusters": int(res["Cdb"]["primary_cluster"].nunique())}
+        if weights is not None:
+            out["shard_weights"] = [float(weights[m].sum()) for m in balanced_shards(weights, world)]
+            out["shard_genomes"] = [int(len(m)) for m in balanced_shards(weights, world)]
+        out["pairs_per_s_job"] = out["pairs"] / sum(v for k, v in res["times"].items())
+        if a.out:
+            from .store import store_primary_linkage, store_sparse
+            os.makedirs(a.out, exist_ok=True)
+            sm = res["sparse"]
+            sm.locations = list(locations)
+            sm.length = lengths
+            store_sparse(a.out, sm)
+            store_primary_linkage(a.out, res["linkage"], None, res["arguments"])
+            res["Cdb"].to_csv(os.path.join(a.out, "primary_Cdb.csv"), index=False)
+            out["stored"] = a.out
+        print(json.dumps(out), flush=True)
     return 0
 
 

@@ -192,6 +192,55 @@ def exchange_screen_parts(cells, ncells: int, records, nrec: int, checks: int, r
     return torch.cat(got_c).contiguous(), torch.cat(got_r).contiguous(), total_checks
 
 
+def gather_pair_lists(rec, n: int, root: int = 0, group=None):
+    """Every rank's pair list -> one list on the root, in rank order.
+
+    rec: this rank's records as an [>= n, 4] int32 tensor (rows past n
+    ignored; n = 0 is legal), on the rank's GPU with nccl, on the CPU or a GPU
+    with gloo (device lists are staged through the host there, as
+    distributed.gather_segments stages its segments).  The counts go by one
+    all-gather; the payloads by one batch_isend_irecv of int8 views, the root
+    posting a receive per non-empty list straight into its slice of the
+    result.  Returns the [sum n, 4] tensor on the root (on rec's device), None
+    elsewhere."""
+    import torch
+    import torch.distributed as dist
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    n = int(n)
+    if rec.dim() != 2 or rec.shape[1] != 4 or rec.dtype != torch.int32 or rec.shape[0] < n:
+        raise ValueError("rec must be an int32 [>= n, 4] tensor")
+    dev = rec.device
+    host = dist.get_backend(group) == "gloo" and rec.is_cuda
+    cdev = torch.device("cpu") if host or not rec.is_cuda else dev
+    counts = torch.empty(world, dtype=torch.int64, device=cdev)
+    dist.all_gather_into_tensor(counts, torch.tensor([n], dtype=torch.int64, device=cdev), group=group)
+    counts = [int(x) for x in counts.cpu()]
+    ops, full, landing = [], None, None
+    if rank == root:
+        full = torch.empty((sum(counts), 4), dtype=torch.int32, device=dev)
+        landing = torch.empty((sum(counts), 4), dtype=torch.int32) if host else full
+        o = 0
+        for r, c in enumerate(counts):
+            if c and r == root:
+                full[o:o + c].copy_(rec[:c])
+            elif c:
+                ops.append(dist.P2POp(dist.irecv, landing[o:o + c].view(torch.int8), r, group))
+            o += c
+    elif n:
+        mine = rec[:n].contiguous()
+        ops.append(dist.P2POp(dist.isend, (mine.cpu() if host else mine).view(torch.int8), root, group))
+    if ops:
+        for req in dist.batch_isend_irecv(ops):
+            req.wait()
+    if rank == root and host:
+        o = 0
+        for r, c in enumerate(counts):
+            if c and r != root:
+                full[o:o + c].copy_(landing[o:o + c])
+            o += c
+    return full
+
+
 def assemble_condensed(N: int, segments: Sequence[np.ndarray], world: int) -> np.ndarray:
     """Concatenate per-rank condensed segments (rank order) into the full
     condensed vector, checking every segment has its expected size."""

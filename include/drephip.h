@@ -319,7 +319,10 @@ int drephip_last_screen_stats(drephip_ctx *ctx, int *used, uint64_t *entries, ui
  * sets *applies when this context screens N genomes at all -- mode, N, N x s --
  * and *use when it would screen them with those checks, as
  * drephip_allpairs_device decides), *n_cells = its marked cell words,
- * *n_records = its runs-of-two records.  Blocking.  Results stay in the
+ * *n_records = its runs-of-two records.  The part's bitmap of every row is
+ * walked in blocks of row tiles (an eighth of the free device memory per
+ * block; DREPHIP_SCREEN_PART_BLOCK_TILES sets the tiles per block, tests): the
+ * cells come out in the same order whatever the blocks.  Blocking.  Results stay in the
  * context until drephip_screen_part_copy copies them out, each as 4 uint32:
  *   cell   {T, w, bits, 0}: columns 32 w + b (bit b set) of row tile T marked
  *   record {a, b, (i << 16) | j, 0}: genomes a < b hold one hash at positions
@@ -369,6 +372,36 @@ int drephip_allpairs_device_marked(drephip_ctx *ctx, const uint64_t *d_hashes, c
 int drephip_allpairs_sparse_device(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash,
                                    uint32_t N, uint32_t row0, uint32_t row1,
                                    uint32_t *d_pairs /* cap x 4 */, uint64_t cap, uint64_t *n_pairs, void *stream);
+/* The sharded form: drephip_allpairs_sparse_device over rows [row0, row1)
+ * screened from the cells and records given -- every hash part's marks of the
+ * sharded screen (drephip_screen_part, routed as for
+ * drephip_allpairs_device_marked); marks of other rows are ignored.  The
+ * record contract is the one above; a pair belongs to the call that owns its
+ * smaller genome, so the lists of disjoint row ranges never share a pair and
+ * those of a partition of [0, N) together are the whole list.
+ *
+ * With the whole-row tables (s <= 2048) the rows are walked in blocks as
+ * above (a multiple of R rows, the same budget, DREPHIP_SPARSE_BLOCK_ROWS);
+ * per block the cells are clipped to its rows, the pair map is built from the
+ * records of its rows, and every pair has one writer: a pair held by a single
+ * run of two, both sketches full, in an unmarked cell is appended by the
+ * screen (common 1 when its rank sum is below s, else nothing); every other
+ * pair -- two runs of two (one per hash part), a partial sketch, a cell a
+ * longer run of any part marked -- goes to the LIST kernel.  No light cells.
+ * A tile that straddles row0, row1 or a block edge gets a superset of marks
+ * and still emits only the rows it owns.  The band path (s > 2048) and a block
+ * whose pair map or lists outgrow the screen's limits run
+ * drephip_allpairs_device_marked into the temporary segment and compact it.
+ * Errors as drephip_allpairs_device_marked: DREPHIP_ERR_ARG for null pointers
+ * and DREPHIP_AP_MERGE, DREPHIP_ERR_UNSUPPORTED for N x s >= 2^32; and
+ * DREPHIP_ERR_NOMEM as above.  Stats as after drephip_allpairs_sparse_device
+ * (entries, runs and checks: the hash part this context grouped last). */
+int drephip_allpairs_sparse_device_marked(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash,
+                                          uint32_t N, uint32_t row0, uint32_t row1,
+                                          const uint32_t *d_cells, uint64_t n_cells,
+                                          const uint32_t *d_records, uint64_t n_records,
+                                          uint32_t *d_pairs /* cap x 4 */, uint64_t cap, uint64_t *n_pairs,
+                                          void *stream);
 /* The host form: sketches checked as drephip_allpairs requires them (rows
  * ascending and distinct, UINT64_MAX past nhash[i]; DREPHIP_ERR_ARG otherwise). */
 int drephip_allpairs_sparse(drephip_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash, uint32_t N,
