@@ -1704,7 +1704,7 @@ int allpairs_geometry(drephip_ctx *ctx, uint32_t *R_out, int *path_out) {
 
 int allpairs_device_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
                          uint32_t row0, uint32_t row1, uint16_t *d_common, uint16_t *d_denom,
-                         hipStream_t st, bool force_merge, bool defer) {
+                         hipStream_t st, bool force_merge, bool defer, const ExtMarks *marks) {
     // an earlier deferred call completes first (its queued item-list copy
     // reads host memory this call may replace)
     if (ctx->apend.active) {
@@ -1735,12 +1735,11 @@ int allpairs_device_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
     const char *mn = getenv("DREPHIP_SCREEN_MIN_N");
     const uint32_t min_n = mn ? (uint32_t)atoi(mn) : kScreenMinN;
     ScreenResult scr;
-    if (ctx->ext.active) {
+    if (marks) {
         // the sharded screen: this call's rows from the parts' marks
         // (drephip_allpairs_device_marked); no light cells
         int rc = screen_marked_impl(ctx, d_nhash, N, row0, row1, R, path == DREPHIP_AP_BAND ? kBandCols : kListCols,
-                                    seg0, npairs, d_common, d_denom, ctx->ext.cells, ctx->ext.ncells, ctx->ext.rec,
-                                    ctx->ext.nrec, st, &scr);
+                                    seg0, npairs, d_common, d_denom, *marks, st, &scr);
         if (rc) return rc;
         ctx->last_screen = scr;
     } else if (smode == DREPHIP_SCREEN_ON || (smode == DREPHIP_SCREEN_AUTO && N >= min_n)) {

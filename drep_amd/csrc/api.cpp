@@ -808,10 +808,9 @@ DREPHIP_EXPORT int drephip_allpairs_device_marked(drephip_ctx *ctx, const uint64
     if ((uint64_t)N * ctx->s >= (1ull << 32)) { set_error("the screen needs N x s < 2^32"); return DREPHIP_ERR_UNSUPPORTED; }
     if (ctx->ap_path == DREPHIP_AP_MERGE) { set_error("marks need the table or band path"); return DREPHIP_ERR_ARG; }
     timing_begin(ctx);
-    ctx->ext = ExtMarks{true, (const uint4 *)d_cells, n_cells, (const uint4 *)d_records, n_records};
+    const ExtMarks marks{(const uint4 *)d_cells, n_cells, (const uint4 *)d_records, n_records};
     int rc = allpairs_device_impl(ctx, d_hashes, d_nhash, N, row0, row1, d_common, d_denom, pick_stream(ctx, stream),
-                                  false);
-    ctx->ext = ExtMarks{};
+                                  false, false, &marks);
     if (rc) return rc;
     timing_collect(ctx);
     return DREPHIP_OK;
@@ -908,10 +907,9 @@ DREPHIP_EXPORT int drephip_allpairs_sparse_device_marked(drephip_ctx *ctx, const
     if ((uint64_t)N * ctx->s >= (1ull << 32)) { set_error("the screen needs N x s < 2^32"); return DREPHIP_ERR_UNSUPPORTED; }
     if (ctx->ap_path == DREPHIP_AP_MERGE) { set_error("marks need the table or band path"); return DREPHIP_ERR_ARG; }
     timing_begin(ctx);
-    ctx->ext = ExtMarks{true, (const uint4 *)d_cells, n_cells, (const uint4 *)d_records, n_records};
+    const ExtMarks marks{(const uint4 *)d_cells, n_cells, (const uint4 *)d_records, n_records};
     int rc = allpairs_sparse_impl(ctx, d_hashes, d_nhash, N, row0, row1, (uint4 *)d_pairs, cap, n_pairs,
-                                  pick_stream(ctx, stream));
-    ctx->ext = ExtMarks{};
+                                  pick_stream(ctx, stream), &marks);
     if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
     timing_collect(ctx);
     return rc;

@@ -107,11 +107,10 @@ struct PartResult {
     uint32_t nrec = 0;
     uint64_t entries = 0, runs = 0, checks = 0;
 };
-// Marks handed to the next all-pairs call (drephip_allpairs_device_marked,
+// Marks handed to an all-pairs call (drephip_allpairs_device_marked,
 // drephip_allpairs_sparse_device_marked): the parts' cell words and records;
-// the call screens its rows from them.
+// the call screens its rows from them.  Passed as an argument (null: no marks).
 struct ExtMarks {
-    bool active = false;
     const uint4 *cells = nullptr;
     uint64_t ncells = 0;
     const uint4 *rec = nullptr;
@@ -142,7 +141,6 @@ struct drephip_ctx {
     ScreenResult last_screen; // the last all-pairs call's screen (stats; pointers into scratch)
     SparseStats sparse;       // the last sparse all-pairs call
     PartResult part;          // the last sharded-screen part (drephip_screen_part)
-    ExtMarks ext;             // marks for the current drephip_allpairs_[sparse_]device_marked call
     int link_path = 0;        // DREPHIP_LINK_PATH_*: 0 auto (sparse when it applies, else dense)
     uint32_t band_cap = 1024; // elements per row per band of the banded all-pairs kernel (clamped to its LDS budget)
     uint32_t band_round = 0;  // elements per row per value round of the band kernel (0: no rounds; A/B)
@@ -235,7 +233,8 @@ int synth_device_impl(drephip_ctx *ctx, uint64_t seed, uint32_t g0, uint32_t n, 
                       uint64_t L, uint32_t *d_codes, uint32_t *d_valid, hipStream_t st);
 int allpairs_device_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash,
                          uint32_t N, uint32_t row0, uint32_t row1, uint16_t *d_common,
-                         uint16_t *d_denom, hipStream_t st, bool force_merge, bool defer = false);
+                         uint16_t *d_denom, hipStream_t st, bool force_merge, bool defer = false,
+                         const ExtMarks *marks = nullptr);   // marks: the rows screened from them (screen_marked_impl)
 int allpairs_wait_impl(drephip_ctx *ctx);
 // The shared-hash screen (screen.hip): the (row tile of R rows, column) cells
 // of rows [row0, row1) whose row and column share a hash, as per-tile column
@@ -256,8 +255,7 @@ int screen_part_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t 
                      uint32_t *nrec);
 int screen_marked_impl(drephip_ctx *ctx, const uint32_t *d_nhash, uint32_t N, uint32_t row0, uint32_t row1,
                        uint32_t R, uint32_t C, uint64_t seg0, uint64_t npairs, uint16_t *d_common, uint16_t *d_denom,
-                       const uint4 *d_cells, uint64_t ncells, const uint4 *d_rec, uint64_t nrec, hipStream_t st,
-                       ScreenResult *res);
+                       const ExtMarks &marks, hipStream_t st, ScreenResult *res);
 // the dense-set rule on the whole triangle's pair checks E
 bool screen_worth(uint32_t N, uint32_t s, uint64_t E);
 // rows per row tile and the all-pairs path (table / band) the all-pairs call
@@ -275,12 +273,12 @@ constexpr uint32_t kListCols = 512;             // screened columns per whole-ro
 // The sparse all-pairs call (sparse.h; driver in screen.hip): rows [row0, row1)
 // as records {i, j, common, denom} of the pairs with common > 0 only, no
 // condensed vector.  *n_pairs = the records the rows hold (> cap: the list is
-// incomplete, nothing is stored past cap).  Blocking.  With ctx->ext active
-// the rows are screened from the given marks instead of a grouping of their own.
+// incomplete, nothing is stored past cap).  Blocking.  With marks given the
+// rows are screened from them instead of a grouping of their own.
 struct SparseOut;
 int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
                          uint32_t row0, uint32_t row1, uint4 *d_pairs, uint64_t cap, uint64_t *n_pairs,
-                         hipStream_t st);
+                         hipStream_t st, const ExtMarks *marks = nullptr);
 // allpairs.hip: the whole-row LIST kernel in its SPARSE flavour over the
 // screened items of rows [row0, row1) (tables built here; queued, no sync), and
 // the bytes of table image a row takes

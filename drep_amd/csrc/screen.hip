@@ -1012,6 +1012,11 @@ struct ScreenProf {
     }
 };
 
+// workgroups of kScWG threads for n elements: at least one, at most cap
+static inline uint32_t grid_for(uint64_t n, uint32_t cap) {
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cap, (n + kScWG - 1) / kScWG));
+}
+
 template <class I, class T>
 static int hip_scan(drephip_ctx *ctx, const char *name, const I *in, T *out, uint32_t n, hipStream_t st) {
     size_t tb = 0;
@@ -1267,6 +1272,176 @@ static uint32_t tile_shift(uint32_t R) {
     return rshift;
 }
 
+// ------------------------------------------------------------ one row block
+// Rows [row0, row1) screened (screen_block): the cell bitmap and the pair map
+// filled, the pairs sharing exactly one hash written (k_screen_simple), the
+// light cells if wanted, the lists.  Every caller differs on two axes only:
+//
+//   source  own grouping  this call's ScreenFront: screen_mark_runs +
+//                         k_screen_mark2 (source_front)
+//           marks         every hash part's cells and records (ExtMarks):
+//                         k_rec_count, k_cells_scatter + k_screen_map2
+//                         (source_marks); no light cells -- a cell's single
+//                         marking run may live in another part
+//   sink    condensed     the no-shared-hash fill first, then
+//                         k_screen_simple<false> once
+//           pair list     no fill; k_screen_simple<true> in phase 0 before the
+//                         lists and, once they are known to fit, in phase 1
+//
+//                      condensed segment       pair list (SparseOut)
+//   own grouping       screen_impl             allpairs_sparse_impl
+//   marks              screen_marked_impl      allpairs_sparse_impl (marked)
+struct BlockSource {
+    const ScreenFront *F = nullptr;       // own grouping (and the hashes), or
+    const uint64_t *d_hashes = nullptr;
+    const ExtMarks *marks = nullptr;      // the parts' marks
+};
+struct BlockSink {
+    uint64_t seg0 = 0, npairs = 0;        // the condensed segment (common != nullptr), or
+    uint16_t *common = nullptr, *denom = nullptr;
+    SparseOut out{};                      // the pair list
+};
+// what a source fills
+struct BlockMaps {
+    uint32_t N, row0, row1, rshift, NW;
+    uint32_t *bm = nullptr, *bmH = nullptr, *crun = nullptr;      // cells; heavy cells and first runs (light)
+    uint64_t pcap = 0;
+    unsigned long long *pkey = nullptr;
+    uint32_t *pcnt = nullptr, *ppos = nullptr;
+};
+
+// The two sources, one signature: the marks of rows [row0, row1) into the
+// (cleared) bitmap, the nkeys pair-map keys into the (cleared) pair map.
+static int source_front(drephip_ctx *ctx, const BlockSource &src, const BlockMaps &B, uint64_t nkeys, hipStream_t st,
+                        ScreenProf &prof) {
+    const ScreenFront &F = *src.F;
+    int rc;
+    if ((rc = screen_mark_runs(ctx, F, src.d_hashes, B.N, B.row0, B.row1, B.rshift, B.NW, B.bm, B.bmH, B.crun, st, prof)))
+        return rc;
+    if (nkeys)
+        hipLaunchKernelGGL(k_screen_mark2, dim3(grid_for(F.n2, 8192)), dim3(kScWG), 0, st, F.v_out, src.d_hashes, ctx->s,
+                           F.vmask, F.pairs, F.n2, B.row0, B.row1, B.pkey, B.pcnt, B.ppos, (uint32_t)(B.pcap - 1));
+    return DREPHIP_OK;
+}
+// The cells clipped to the rows, the map from the records of these rows.  A
+// part's tile that straddles the first or last row gives its whole word to the
+// tiles it touches -- a superset, which costs LIST work only: the LIST kernel
+// writes the rows [row0, row1) of a marked cell and nothing else, and
+// k_screen_simple skips every pair of a marked cell.  A pair held by runs of
+// two in two parts arrives as two records of one key (pcnt 2: the LIST
+// kernel's); one held by a run of two here and a longer run there finds its
+// cell marked by the cells.
+static int source_marks(drephip_ctx *, const BlockSource &src, const BlockMaps &B, uint64_t nkeys, hipStream_t st,
+                        ScreenProf &prof) {
+    const ExtMarks &m = *src.marks;
+    if (m.ncells)
+        hipLaunchKernelGGL(k_cells_scatter, dim3(grid_for(m.ncells, 4096)), dim3(kScWG), 0, st, m.cells, m.ncells, B.row0,
+                           B.row1, B.rshift, B.NW, B.bm);
+    prof.mark("cells", st);
+    if (nkeys)
+        hipLaunchKernelGGL(k_screen_map2, dim3(grid_for(m.nrec, 8192)), dim3(kScWG), 0, st, m.rec, m.nrec, B.row0, B.row1,
+                           B.pkey, B.pcnt, B.ppos, (uint32_t)(B.pcap - 1));
+    return DREPHIP_OK;
+}
+
+// this rank's own part (the entries it grouped), for the stats of a marked call
+static void own_part_stats(const drephip_ctx *ctx, uint32_t N, ScreenResult *res) {
+    if (!ctx->part.valid || ctx->part.N != N) return;
+    res->entries = ctx->part.entries;
+    res->runs = ctx->part.runs;
+    res->checks = ctx->part.checks;
+}
+
+// The driver.  res (its stats set by the caller) gets the lists, marked and
+// simple; res->use stays false, with nothing written that a later path does
+// not rewrite, when the pair map would exceed kMaxPairMap or the lists do not
+// fit: the caller gives way to the dense path / the fallback.  Light cells
+// (k_screen_light; own grouping only) when want_light and they fit
+// kLightBudget; a pair-list block with light cells has appended pairs before
+// the lists are known to fit, so there that is an error.  *d_nsimple_out: the
+// device counter behind res->simple, which phase 1 goes on adding to.
+static int screen_block(drephip_ctx *ctx, const BlockSource &src, const BlockSink &sink, const uint32_t *d_nhash,
+                        uint32_t N, uint32_t row0, uint32_t row1, uint32_t R, uint32_t C, bool want_light,
+                        hipStream_t st, ScreenProf &prof, ScreenResult *res,
+                        unsigned long long **d_nsimple_out = nullptr) {
+    const bool own = src.F != nullptr, sparse = sink.common == nullptr;
+    const bool phases = own && !sparse;               // screen_impl's finer ScreenProf labels
+    const uint32_t s = ctx->s, ntiles = (row1 - row0 + R - 1) / R;
+    BlockMaps B{N, row0, row1, tile_shift(R), (N + 31) / 32};
+    const uint64_t nwords = (uint64_t)ntiles * B.NW;
+    int rc;
+    unsigned long long *d_nsimple;
+    if ((rc = scratch(ctx, "sc_bitmap", nwords * 4, (void **)&B.bm))) return rc;
+    if ((rc = scratch(ctx, "sc_nsimple", 8, (void **)&d_nsimple))) return rc;
+    // light cells: a heavy-cell bitmap and each cell's first marking run, (ntiles x N) words
+    const bool light = own && want_light && (uint64_t)ntiles * N * 4 <= kLightBudget;
+    if (light) {
+        if ((rc = scratch(ctx, "sc_bitmap_heavy", nwords * 4, (void **)&B.bmH))) return rc;
+        if ((rc = scratch(ctx, "sc_crun", (uint64_t)ntiles * N * 4, (void **)&B.crun))) return rc;
+    }
+    // the pair map, twice its keys: the runs of two, or this block's records
+    // (every part's records of its rows, counted here)
+    uint64_t nkeys = own ? src.F->n2 : 0;
+    if (!own && src.marks->nrec) {
+        uint64_t *h_tot;
+        if ((rc = pinned_host(ctx, "sc_tot", 64, (void **)&h_tot))) return rc;
+        HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
+        hipLaunchKernelGGL(k_rec_count, dim3(grid_for(src.marks->nrec, 1024)), dim3(kScWG), 0, st, src.marks->rec,
+                           src.marks->nrec, row0, row1, d_nsimple);
+        HIPC(hipMemcpyAsync(h_tot, d_nsimple, 8, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        nkeys = h_tot[0];
+    }
+    if ((rc = screen_pair_map(ctx, nkeys, st, &B.pcap, &B.pkey, &B.pcnt, &B.ppos))) return rc;
+    if (B.pcap > kMaxPairMap) return DREPHIP_OK;
+    if (phases) prof.mark("readback+alloc", st);
+    if (!sparse) {
+        // every pair as no-shared-hash first: the simple pairs are written over
+        // it below, the LIST kernel over both
+        if ((rc = screen_fill_impl(ctx, d_nhash, N, row0, row1, sink.seg0, sink.npairs, sink.common, sink.denom, st)))
+            return rc;
+        if (phases) prof.mark("fill", st);
+    }
+    HIPC(hipMemsetAsync(B.bm, 0, nwords * 4, st));
+    if (light) HIPC(hipMemsetAsync(B.bmH, 0, nwords * 4, st));
+    HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
+    if (phases) prof.mark("bitmap-clear", st);
+    if ((rc = (own ? source_front : source_marks)(ctx, src, B, nkeys, st, prof))) return rc;
+    // the sink's flavour of the two kernels that write pairs
+    struct PairKernels { decltype(&k_screen_simple<false>) simple; decltype(&k_screen_light<false>) light; };
+    const PairKernels k = !sparse ? PairKernels{k_screen_simple<false>, k_screen_light<false>}
+                                  : PairKernels{k_screen_simple<true>, k_screen_light<true>};
+    auto simple = [&](int phase) {
+        hipLaunchKernelGGL(k.simple, dim3(grid_for(B.pcap, 2048)), dim3(kScWG), 0, st, B.pkey, B.pcnt, B.ppos,
+                           (uint32_t)B.pcap, d_nhash, s, N, row0, B.rshift, B.NW, sink.seg0, B.bm, B.bmH, sink.common,
+                           d_nsimple, sink.out, phase);
+    };
+    if (nkeys) simple(0);
+    prof.mark(own ? "mark" : "pairs", st);
+    HIPC(hipGetLastError());
+    // the cells left to the LIST kernels: all marked ones, or (light) the heavy
+    // ones -- final only after k_screen_light, which therefore runs before the
+    // lists (and, into a pair list, appends)
+    if (light && src.F->nruns) {
+        const ScreenFront &F = *src.F;
+        hipLaunchKernelGGL(k.light, dim3(grid_for(nwords, 4096)), dim3(kScWG), 0, st, B.bm, B.bmH, B.crun, F.runs, F.v_out,
+                           src.d_hashes, d_nhash, s, F.vmask, N, row0, row1, R, B.NW, nwords, sink.seg0, sink.common,
+                           d_nsimple, sink.out);
+        prof.mark("light", st);
+    }
+    if ((rc = screen_lists(ctx, light ? B.bmH : B.bm, ntiles, B.NW, C, row0, R, d_nsimple, st, prof, res))) return rc;
+    if (sparse && res->use) {
+        // every mark is in place and the block is known to fit: the pairs of one run of two
+        if (nkeys) simple(1);
+        HIPC(hipGetLastError());
+    } else if (sparse && light) {
+        set_error("sparse all-pairs: the light screen's block outgrew the list limits");
+        return DREPHIP_ERR_INTERNAL;
+    }
+    if (d_nsimple_out) *d_nsimple_out = d_nsimple;
+    return DREPHIP_OK;
+}
+
 // the dense-set rule: a pair check costs about as much as a few probes of the
 // dense kernels, which make ~s/2 probes per pair (DREPHIP_SCREEN_RATIO scales
 // the bound).  E counts the checks of the whole triangle (every entry is
@@ -1315,7 +1490,7 @@ int screen_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nh
             hipLaunchKernelGGL(k_cmask_init, dim3((N + kScWG - 1) / kScWG), dim3(kScWG), 0, st, d_nhash, N, F.k_out, F.M,
                                d_cm);
             if (F.n2)
-                hipLaunchKernelGGL(k_cmask_pairs, dim3(std::min(4096u, (F.n2 + kScWG - 1) / kScWG)), dim3(kScWG), 0, st,
+                hipLaunchKernelGGL(k_cmask_pairs, dim3(grid_for(F.n2, 4096)), dim3(kScWG), 0, st,
                                    F.v_out, d_hashes, s, F.vmask, F.pairs, F.n2, d_cm);
             if (F.nruns)
                 hipLaunchKernelGGL(k_cmask_runs, dim3(std::min(4096u, (F.nruns + 3) / 4)), dim3(kScWG), 0, st, F.v_out,
@@ -1329,61 +1504,16 @@ int screen_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nh
         return DREPHIP_OK;
     }
 
-    const uint32_t rows = row1 - row0;
-    const uint32_t ntiles = (rows + R - 1) / R;
-    const uint32_t NW = (N + 31) / 32;
-    const uint32_t rshift = tile_shift(R);
-    uint32_t *d_bm;
-    if ((rc = scratch(ctx, "sc_bitmap", (uint64_t)ntiles * NW * 4, (void **)&d_bm))) return rc;
-    // Light cells (k_screen_light): a heavy-cell bitmap and each cell's first
-    // marking run, (ntiles x N) words -- taken when that fits kLightBudget
+    // Light cells (k_screen_light) are taken when they fit kLightBudget
     // (N = 10^4 with R = 4: 100 MB), for the band kernel only: at configs[4]
     // its LIST time 9.0 -> 4.0 ms for +0.9 ms of screen; at configs[2] (the q
     // kernel, s = 1000) 0.39 -> 0.35 ms of LIST for +0.33 ms of screen
     // (profiles/r05_screen_light_c2_ab.txt).  DREPHIP_SCREEN_LIGHT=0/1 forces it (A/B)
     const char *le = getenv("DREPHIP_SCREEN_LIGHT");
-    const bool light = (le ? atoi(le) != 0 : band) && (uint64_t)ntiles * N * 4 <= kLightBudget;
-    uint32_t *d_bmH = nullptr, *d_crun = nullptr;
-    if (light) {
-        if ((rc = scratch(ctx, "sc_bitmap_heavy", (uint64_t)ntiles * NW * 4, (void **)&d_bmH))) return rc;
-        if ((rc = scratch(ctx, "sc_crun", (uint64_t)ntiles * N * 4, (void **)&d_crun))) return rc;
-    }
-    // the pair map of the runs of two (k_screen_mark2), twice their count; a
-    // map beyond kMaxPairMap slots (16 B each) is not built: the dense path runs
-    uint64_t pcap;
-    unsigned long long *pkey = nullptr, *d_nsimple;
-    uint32_t *pcnt = nullptr, *ppos = nullptr;
-    if ((rc = screen_pair_map(ctx, F.n2, st, &pcap, &pkey, &pcnt, &ppos))) return rc;
-    if (pcap > kMaxPairMap) { timing_mark(ctx, 4, st, false); return DREPHIP_OK; }
-    if ((rc = scratch(ctx, "sc_nsimple", 8, (void **)&d_nsimple))) return rc;
-    prof.mark("readback+alloc", st);
-    // every pair as no-shared-hash first: the simple pairs are written over it
-    // below, the LIST kernel over both
-    if ((rc = screen_fill_impl(ctx, d_nhash, N, row0, row1, seg0, npairs, d_common, d_denom, st))) return rc;
-    prof.mark("fill", st);
-    HIPC(hipMemsetAsync(d_bm, 0, (uint64_t)ntiles * NW * 4, st));
-    if (light) HIPC(hipMemsetAsync(d_bmH, 0, (uint64_t)ntiles * NW * 4, st));
-    HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
-    prof.mark("bitmap-clear", st);
-    if ((rc = screen_mark_runs(ctx, F, d_hashes, N, row0, row1, rshift, NW, d_bm, d_bmH, d_crun, st, prof))) return rc;
-    if (F.n2) {
-        const uint32_t g2 = std::max(1u, std::min(8192u, (F.n2 + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_mark2, dim3(g2), dim3(kScWG), 0, st, F.v_out, d_hashes, s, F.vmask, F.pairs, F.n2, row0, row1,
-                           pkey, pcnt, ppos, (uint32_t)(pcap - 1));
-        const uint32_t gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (pcap + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_simple<false>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
-                           row0, rshift, NW, seg0, d_bm, d_bmH, d_common, d_nsimple, SparseOut{}, 0);
-    }
-    prof.mark("mark", st);
-    if (light && F.nruns) {
-        const uint64_t nwords = (uint64_t)ntiles * NW;
-        const uint32_t gl = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, (nwords + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_light<false>, dim3(gl), dim3(kScWG), 0, st, d_bm, d_bmH, d_crun, F.runs, F.v_out, d_hashes,
-                           d_nhash, s, F.vmask, N, row0, row1, R, NW, nwords, seg0, d_common, d_nsimple, SparseOut{});
-        prof.mark("light", st);
-    }
-    // the LIST kernels take the heavy cells (every marked cell without the light screen)
-    rc = screen_lists(ctx, light ? d_bmH : d_bm, ntiles, NW, C, row0, R, d_nsimple, st, prof, res);
+    const BlockSource src{&F, d_hashes};
+    const BlockSink sink{seg0, npairs, d_common, d_denom};
+    // (a pair map beyond kMaxPairMap slots is not built: the dense path runs)
+    rc = screen_block(ctx, src, sink, d_nhash, N, row0, row1, R, C, le ? atoi(le) != 0 : band, st, prof, res);
     timing_mark(ctx, 4, st, false);
     return rc;
 }
@@ -1432,11 +1562,9 @@ int screen_part_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t 
     if ((rc = scratch(ctx, "sc_part_nrec", 8, (void **)&d_nrec))) return rc;
     if ((rc = scratch(ctx, "sc_part_rec", (uint64_t)std::max<uint32_t>(F.n2, 1) * 16, (void **)&d_rec))) return rc;
     HIPC(hipMemsetAsync(d_nrec, 0, 4, st));
-    if (F.M >= 2 && F.n2) {
-        const uint32_t g2 = std::max(1u, std::min(8192u, (F.n2 + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_emit2, dim3(g2), dim3(kScWG), 0, st, F.v_out, d_hashes, s, F.vmask, F.pairs, F.n2,
-                           d_rec, d_nrec);
-    }
+    if (F.M >= 2 && F.n2)
+        hipLaunchKernelGGL(k_screen_emit2, dim3(grid_for(F.n2, 8192)), dim3(kScWG), 0, st, F.v_out, d_hashes, s, F.vmask,
+                           F.pairs, F.n2, d_rec, d_nrec);
     uint64_t *h_tot;
     if ((rc = pinned_host(ctx, "sc_tot", 64, (void **)&h_tot))) return rc;
     HIPC(hipMemcpyAsync(h_tot + 1, d_nrec, 4, hipMemcpyDeviceToHost, st));
@@ -1505,68 +1633,20 @@ int screen_part_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t 
     return DREPHIP_OK;
 }
 
-// Rows [row0, row1) from every part's marks: the cell words OR-ed into this
-// rank's row tiles, the pair map from every part's records of these rows, the
-// pairs sharing exactly one hash written here (k_screen_simple), the lists.
-// No light cells (their single marking run may live in another part).
+// Rows [row0, row1) of a rank of a sharded job into the condensed segment,
+// screened from every part's marks (screen_block).
 int screen_marked_impl(drephip_ctx *ctx, const uint32_t *d_nhash, uint32_t N, uint32_t row0, uint32_t row1,
                        uint32_t R, uint32_t C, uint64_t seg0, uint64_t npairs, uint16_t *d_common, uint16_t *d_denom,
-                       const uint4 *d_cells, uint64_t ncells, const uint4 *d_rec, uint64_t nrec, hipStream_t st,
-                       ScreenResult *res) {
+                       const ExtMarks &marks, hipStream_t st, ScreenResult *res) {
     *res = ScreenResult{};
-    const uint32_t s = ctx->s;
-    int rc;
+    own_part_stats(ctx, N, res);
     timing_mark(ctx, 4, st, true);
     ScreenProf prof;
     prof.mark("start", st);
-    const uint32_t rows = row1 - row0, ntiles = (rows + R - 1) / R, NW = (N + 31) / 32;
-    const uint32_t rshift = tile_shift(R);
-    uint32_t *d_bm;
-    unsigned long long *pkey = nullptr, *d_nsimple;
-    uint32_t *pcnt = nullptr, *ppos = nullptr;
-    uint64_t pcap;
-    if ((rc = scratch(ctx, "sc_bitmap", (uint64_t)ntiles * NW * 4, (void **)&d_bm))) return rc;
-    if ((rc = scratch(ctx, "sc_nsimple", 8, (void **)&d_nsimple))) return rc;
-    // the pair map holds this rank's records only (every part's records of its rows)
-    uint64_t nown = 0;
-    if (nrec) {
-        uint64_t *h_tot;
-        if ((rc = pinned_host(ctx, "sc_tot", 64, (void **)&h_tot))) return rc;
-        HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
-        const uint32_t gc = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1024, (nrec + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_rec_count, dim3(gc), dim3(kScWG), 0, st, d_rec, nrec, row0, row1, d_nsimple);
-        HIPC(hipMemcpyAsync(h_tot, d_nsimple, 8, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-        nown = h_tot[0];
-    }
-    if ((rc = screen_pair_map(ctx, nown, st, &pcap, &pkey, &pcnt, &ppos))) return rc;
-    if (pcap > kMaxPairMap) { timing_mark(ctx, 4, st, false); return DREPHIP_OK; }
-    if ((rc = screen_fill_impl(ctx, d_nhash, N, row0, row1, seg0, npairs, d_common, d_denom, st))) return rc;
-    HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
-    HIPC(hipMemsetAsync(d_bm, 0, (uint64_t)ntiles * NW * 4, st));
-    if (ncells) {
-        const uint32_t gc = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, (ncells + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_cells_scatter, dim3(gc), dim3(kScWG), 0, st, d_cells, ncells, row0, row1, rshift, NW, d_bm);
-    }
-    prof.mark("cells", st);
-    if (nown) {
-        const uint32_t g2 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(8192, (nrec + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_map2, dim3(g2), dim3(kScWG), 0, st, d_rec, nrec, row0, row1, pkey, pcnt, ppos,
-                           (uint32_t)(pcap - 1));
-        const uint32_t gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (pcap + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_simple<false>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
-                           row0, rshift, NW, seg0, d_bm, nullptr, d_common, d_nsimple, SparseOut{}, 0);
-    }
-    prof.mark("pairs", st);
-    HIPC(hipGetLastError());
-    rc = screen_lists(ctx, d_bm, ntiles, NW, C, row0, R, d_nsimple, st, prof, res);
+    const BlockSource src{nullptr, nullptr, &marks};
+    const BlockSink sink{seg0, npairs, d_common, d_denom};
+    const int rc = screen_block(ctx, src, sink, d_nhash, N, row0, row1, R, C, false, st, prof, res);
     timing_mark(ctx, 4, st, false);
-    if (ctx->part.valid && ctx->part.N == N) {
-        // this rank's own part (the entries it grouped), for the stats
-        res->entries = ctx->part.entries;
-        res->runs = ctx->part.runs;
-        res->checks = ctx->part.checks;
-    }
     return rc;
 }
 
@@ -1588,16 +1668,18 @@ int screen_fill_impl(drephip_ctx *ctx, const uint32_t *d_nhash, uint32_t N, uint
 // dense verdict): the entries are grouped once per call (screen_front); the
 // rows are then walked in blocks of a multiple of R rows, so that the
 // row-proportional scratch -- the cell bitmap, ntiles x N / 32 words, and the
-// row images -- stays inside a budget.  Per block the marking runs as in
-// screen_impl, without the no-shared-hash fill and without light cells, and
-// every pair has one writer: k_screen_simple<true> for a pair held by one run
-// of two in an unmarked cell, the SPARSE LIST kernel for every pair of a
-// marked cell.
+// row images -- stays inside a budget.  Each block is one screen_block into
+// the pair-list sink: no no-shared-hash fill, light cells only when
+// DREPHIP_SCREEN_LIGHT=1 asks for them (screen_impl takes them by default with
+// the band kernel only), and every pair has one writer: k_screen_simple<true>
+// for a pair held by one run of two in an unmarked cell, the SPARSE LIST
+// kernel for every pair of a marked cell.  A block whose pair map or lists
+// outgrow the screen's limits has appended nothing (res.use false).
 //
 // Marked form (drephip_allpairs_sparse_device_marked, a rank of a sharded
-// job): no grouping here; each block takes its marks from every hash part's
-// cells and records (sparse_marked_block), the fallback's dense call screens
-// its rows from the same marks.
+// job; `marks` given): no grouping here, the caller has taken the screen's
+// verdict; each block takes every hash part's cells and records as its
+// source, and the fallback's dense call screens its rows from the same marks.
 //
 // Fallback (every other plan: band path, screen off or dense verdict, N x s >=
 // 2^32, the literal merge; and the rest of a call once a block's pair map or
@@ -1647,146 +1729,9 @@ __global__ __launch_bounds__(kScWG) void k_sp_write(const uint16_t *__restrict__
     }
 }
 
-// one block of the direct path: marks, lists and the pairs the screen writes
-// itself; res->use = false (nothing appended) when the block outgrows the
-// screen's limits
-static int sparse_direct_block(drephip_ctx *ctx, const ScreenFront &F, const uint64_t *d_hashes,
-                               const uint32_t *d_nhash, uint32_t N, uint32_t row0, uint32_t row1, uint32_t R,
-                               const SparseOut &out, hipStream_t st, ScreenProf &prof, ScreenResult *res,
-                               unsigned long long **d_nsimple_out) {
-    *res = ScreenResult{};
-    *d_nsimple_out = nullptr;
-    res->entries = F.M;
-    if (F.M < 2) {                                   // no two entries: no pair shares a hash
-        res->use = true;
-        return DREPHIP_OK;
-    }
-    res->runs = (uint64_t)F.n2 + F.nruns;
-    res->checks = F.E;
-    const uint32_t s = ctx->s;
-    const uint32_t ntiles = (row1 - row0 + R - 1) / R, NW = (N + 31) / 32, rshift = tile_shift(R);
-    int rc;
-    uint32_t *d_bm;
-    if ((rc = scratch(ctx, "sc_bitmap", (uint64_t)ntiles * NW * 4, (void **)&d_bm))) return rc;
-    uint64_t pcap;
-    unsigned long long *pkey = nullptr, *d_nsimple;
-    uint32_t *pcnt = nullptr, *ppos = nullptr;
-    if ((rc = screen_pair_map(ctx, F.n2, st, &pcap, &pkey, &pcnt, &ppos))) return rc;
-    if (pcap > kMaxPairMap) return DREPHIP_OK;
-    if ((rc = scratch(ctx, "sc_nsimple", 8, (void **)&d_nsimple))) return rc;
-    // light cells (k_screen_light): off on this path unless DREPHIP_SCREEN_LIGHT=1
-    // asks for them (screen_impl takes them by default with the band kernel only)
-    const char *le = getenv("DREPHIP_SCREEN_LIGHT");
-    const bool light = le && atoi(le) != 0 && F.nruns && (uint64_t)ntiles * N * 4 <= kLightBudget;
-    uint32_t *d_bmH = nullptr, *d_crun = nullptr;
-    if (light) {
-        if ((rc = scratch(ctx, "sc_bitmap_heavy", (uint64_t)ntiles * NW * 4, (void **)&d_bmH))) return rc;
-        if ((rc = scratch(ctx, "sc_crun", (uint64_t)ntiles * N * 4, (void **)&d_crun))) return rc;
-        HIPC(hipMemsetAsync(d_bmH, 0, (uint64_t)ntiles * NW * 4, st));
-    }
-    HIPC(hipMemsetAsync(d_bm, 0, (uint64_t)ntiles * NW * 4, st));
-    HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
-    if ((rc = screen_mark_runs(ctx, F, d_hashes, N, row0, row1, rshift, NW, d_bm, d_bmH, d_crun, st, prof))) return rc;
-    const uint32_t gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (pcap + kScWG - 1) / kScWG));
-    if (F.n2) {
-        const uint32_t g2 = std::max(1u, std::min(8192u, (F.n2 + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_mark2, dim3(g2), dim3(kScWG), 0, st, F.v_out, d_hashes, s, F.vmask, F.pairs, F.n2, row0, row1,
-                           pkey, pcnt, ppos, (uint32_t)(pcap - 1));
-        hipLaunchKernelGGL(k_screen_simple<true>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
-                           row0, rshift, NW, 0ull, d_bm, d_bmH, nullptr, d_nsimple, out, 0);
-    }
-    prof.mark("mark", st);
-    // the cells left to the LIST kernel: all marked ones, or (light) the heavy
-    // ones -- final only after k_screen_light, which therefore runs before the
-    // lists and appends; a block that then does not fit the lists' limits
-    // cannot be handed to the fallback any more
-    if (light) {
-        const uint64_t nwords = (uint64_t)ntiles * NW;
-        const uint32_t gl = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, (nwords + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_light<true>, dim3(gl), dim3(kScWG), 0, st, d_bm, d_bmH, d_crun, F.runs, F.v_out, d_hashes,
-                           d_nhash, s, F.vmask, N, row0, row1, R, NW, nwords, 0ull, nullptr, d_nsimple, out);
-        prof.mark("light", st);
-    }
-    if ((rc = screen_lists(ctx, light ? d_bmH : d_bm, ntiles, NW, kListCols, row0, R, d_nsimple, st, prof, res))) return rc;
-    if (!res->use) {
-        if (light) { set_error("sparse all-pairs: the light screen's block outgrew the list limits"); return DREPHIP_ERR_INTERNAL; }
-        return DREPHIP_OK;
-    }
-    // every mark is in place (and the block is known to fit): the pairs of one run of two
-    if (F.n2)
-        hipLaunchKernelGGL(k_screen_simple<true>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
-                           row0, rshift, NW, 0ull, d_bm, d_bmH, nullptr, d_nsimple, out, 1);
-    HIPC(hipGetLastError());
-    *d_nsimple_out = d_nsimple;
-    return DREPHIP_OK;
-}
-
-// one block of the direct path of a marked call (ctx->ext: every hash part's
-// cells and records): the cells clipped to the block's rows, the pair map from
-// the records of these rows, then as sparse_direct_block.  A part's tile that
-// straddles the block's first or last row gives its whole word to the block's
-// tiles it touches -- a superset, which costs LIST work only: the LIST kernel
-// appends the rows [row0, row1) of a marked cell and nothing else, and phase 1
-// skips every pair of a marked cell.  A pair held by runs of two in two parts
-// arrives as two records of one key (pcnt 2: the LIST kernel's); one held by a
-// run of two here and a longer run there finds its cell marked by the cells.
-static int sparse_marked_block(drephip_ctx *ctx, const uint32_t *d_nhash, uint32_t N, uint32_t row0, uint32_t row1,
-                               uint32_t R, const SparseOut &out, hipStream_t st, ScreenProf &prof, ScreenResult *res,
-                               unsigned long long **d_nsimple_out) {
-    *res = ScreenResult{};
-    *d_nsimple_out = nullptr;
-    const ExtMarks &ext = ctx->ext;
-    const uint32_t s = ctx->s;
-    const uint32_t ntiles = (row1 - row0 + R - 1) / R, NW = (N + 31) / 32, rshift = tile_shift(R);
-    int rc;
-    uint32_t *d_bm;
-    unsigned long long *pkey = nullptr, *d_nsimple;
-    uint32_t *pcnt = nullptr, *ppos = nullptr;
-    uint64_t pcap, nown = 0;
-    if ((rc = scratch(ctx, "sc_bitmap", (uint64_t)ntiles * NW * 4, (void **)&d_bm))) return rc;
-    if ((rc = scratch(ctx, "sc_nsimple", 8, (void **)&d_nsimple))) return rc;
-    if (ext.nrec) {
-        uint64_t *h_tot;
-        if ((rc = pinned_host(ctx, "sc_tot", 64, (void **)&h_tot))) return rc;
-        HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
-        const uint32_t gc = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1024, (ext.nrec + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_rec_count, dim3(gc), dim3(kScWG), 0, st, ext.rec, ext.nrec, row0, row1, d_nsimple);
-        HIPC(hipMemcpyAsync(h_tot, d_nsimple, 8, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-        nown = h_tot[0];
-    }
-    if ((rc = screen_pair_map(ctx, nown, st, &pcap, &pkey, &pcnt, &ppos))) return rc;
-    if (pcap > kMaxPairMap) return DREPHIP_OK;
-    HIPC(hipMemsetAsync(d_bm, 0, (uint64_t)ntiles * NW * 4, st));
-    HIPC(hipMemsetAsync(d_nsimple, 0, 8, st));
-    if (ext.ncells) {
-        const uint32_t gc = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, (ext.ncells + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_cells_scatter, dim3(gc), dim3(kScWG), 0, st, ext.cells, ext.ncells, row0, row1, rshift, NW, d_bm);
-    }
-    prof.mark("cells", st);
-    const uint32_t gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (pcap + kScWG - 1) / kScWG));
-    if (nown) {
-        const uint32_t g2 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(8192, (ext.nrec + kScWG - 1) / kScWG));
-        hipLaunchKernelGGL(k_screen_map2, dim3(g2), dim3(kScWG), 0, st, ext.rec, ext.nrec, row0, row1, pkey, pcnt, ppos,
-                           (uint32_t)(pcap - 1));
-        hipLaunchKernelGGL(k_screen_simple<true>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
-                           row0, rshift, NW, 0ull, d_bm, nullptr, nullptr, d_nsimple, out, 0);
-    }
-    prof.mark("pairs", st);
-    HIPC(hipGetLastError());
-    if ((rc = screen_lists(ctx, d_bm, ntiles, NW, kListCols, row0, R, d_nsimple, st, prof, res))) return rc;
-    if (!res->use) return DREPHIP_OK;
-    if (nown)
-        hipLaunchKernelGGL(k_screen_simple<true>, dim3(gs), dim3(kScWG), 0, st, pkey, pcnt, ppos, (uint32_t)pcap, d_nhash, s, N,
-                           row0, rshift, NW, 0ull, d_bm, nullptr, nullptr, d_nsimple, out, 1);
-    HIPC(hipGetLastError());
-    *d_nsimple_out = d_nsimple;
-    return DREPHIP_OK;
-}
-
 int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
                          uint32_t row0, uint32_t row1, uint4 *d_pairs, uint64_t cap, uint64_t *n_pairs,
-                         hipStream_t st) {
+                         hipStream_t st, const ExtMarks *marks) {
     *n_pairs = 0;
     ctx->sparse = SparseStats{};
     if (ctx->apend.active) {
@@ -1812,13 +1757,12 @@ int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
 
     // marks given (drephip_allpairs_sparse_device_marked): the caller has
     // grouped the entries and taken the screen's verdict; the fallback's dense
-    // call below screens its rows from the same marks (ctx->ext)
-    const bool marked = ctx->ext.active;
-    bool direct = path == DREPHIP_AP_TABLE && (marked || screen_applies(ctx, N));
+    // call below screens its rows from the same marks
+    bool direct = path == DREPHIP_AP_TABLE && (marks || screen_applies(ctx, N));
     ScreenProf prof;
     ScreenFront F;
-    if (marked) prof.mark("start", st);
-    if (direct && !marked) {
+    if (marks) prof.mark("start", st);
+    if (direct && !marks) {
         prof.mark("start", st);
         timing_mark(ctx, 4, st, true);
         rc = screen_front(ctx, d_hashes, d_nhash, N, 0, 1, st, prof, &F);
@@ -1840,19 +1784,32 @@ int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
         }
         rows = std::max<uint64_t>(R, (rows + R - 1) / R * R);
         HIPC(hipMemsetAsync(d_count, 0, 8, st));
-        const SparseOut out{d_pairs, d_count, cap};
+        const BlockSource src{marks ? nullptr : &F, d_hashes, marks};
+        BlockSink sink;
+        sink.out = SparseOut{d_pairs, d_count, cap};
+        // every block's stats: the entries grouped here, or (marks) by this rank's own part
+        ScreenResult stats;
+        if (marks) {
+            own_part_stats(ctx, N, &stats);
+        } else {
+            stats.entries = F.M;
+            stats.runs = (uint64_t)F.n2 + F.nruns;
+            stats.checks = F.E;
+        }
+        const char *le = getenv("DREPHIP_SCREEN_LIGHT");
+        const bool want_light = le && atoi(le) != 0 && F.nruns;
         ScreenResult acc;
         while (b0 < row1) {
             const uint32_t b1 = (uint32_t)std::min<uint64_t>(row1, (uint64_t)b0 + rows);
-            ScreenResult res;
+            ScreenResult res = stats;
             unsigned long long *d_nsimple = nullptr;
             timing_mark(ctx, 4, st, true);
-            rc = marked ? sparse_marked_block(ctx, d_nhash, N, b0, b1, R, out, st, prof, &res, &d_nsimple)
-                        : sparse_direct_block(ctx, F, d_hashes, d_nhash, N, b0, b1, R, out, st, prof, &res, &d_nsimple);
+            if (!marks && F.M < 2) res.use = true;    // no two entries: no pair shares a hash
+            else rc = screen_block(ctx, src, sink, d_nhash, N, b0, b1, R, kListCols, want_light, st, prof, &res, &d_nsimple);
             timing_mark(ctx, 4, st, false);
             if (rc) return rc;
             if (!res.use) break;                      // this block and the rest: the fallback
-            if ((rc = allpairs_sparse_list_impl(ctx, d_hashes, d_nhash, N, b0, b1, R, res, out, st))) return rc;
+            if ((rc = allpairs_sparse_list_impl(ctx, d_hashes, d_nhash, N, b0, b1, R, res, sink.out, st))) return rc;
             HIPC(hipMemcpyAsync(h_tot, d_count, 8, hipMemcpyDeviceToHost, st));
             if (d_nsimple) HIPC(hipMemcpyAsync(h_tot + 1, d_nsimple, 8, hipMemcpyDeviceToHost, st));
             HIPC(hipStreamSynchronize(st));
@@ -1865,12 +1822,6 @@ int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
             acc.simple += d_nsimple ? h_tot[1] : 0;
             ctx->sparse.blocks++;
             b0 = b1;
-        }
-        if (marked && acc.use && ctx->part.valid && ctx->part.N == N) {
-            // this rank's own part (the entries it grouped), as screen_marked_impl reports
-            acc.entries = ctx->part.entries;
-            acc.runs = ctx->part.runs;
-            acc.checks = ctx->part.checks;
         }
         ctx->sparse.direct = total;
         ctx->last_screen = acc;                       // (stats only: no list pointers)
@@ -1891,7 +1842,7 @@ int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
         if ((rc = scratch(ctx, "sp_seg_denom", np * 2, (void **)&d_d))) return rc;
         if ((rc = scratch(ctx, "sp_row_cnt", (nrows + 1) * 8ull, (void **)&d_cnt))) return rc;
         if ((rc = scratch(ctx, "sp_row_off", (nrows + 1) * 8ull, (void **)&d_off))) return rc;
-        if ((rc = allpairs_device_impl(ctx, d_hashes, d_nhash, N, b0, b1, d_c, d_d, st, false))) return rc;
+        if ((rc = allpairs_device_impl(ctx, d_hashes, d_nhash, N, b0, b1, d_c, d_d, st, false, false, marks))) return rc;
         const uint64_t seg0 = (uint64_t)b0 * N - (uint64_t)b0 * (b0 + 1) / 2;
         HIPC(hipMemsetAsync(d_cnt + nrows, 0, 8, st));
         hipLaunchKernelGGL(k_sp_count, dim3(nrows), dim3(kScWG), 0, st, d_c, N, b0, seg0, d_cnt);
