@@ -242,7 +242,9 @@ def prefilter_eval(q1: np.ndarray, q2: np.ndarray, T: int) -> Tuple[np.ndarray, 
 
 def canon_eval(words: np.ndarray, r: int) -> Tuple[np.ndarray, np.ndarray]:
     """drephip_canon_eval (host): (high word, tail index) of the canonical 21-mer
-    ending at base 32 + r of each row of words (n x 3 code words)."""
+    ending at base 32 + r of each row of words (n x 3 code words).  The tail is
+    the natural index (base 16 on top): the kernel's table index -- the other
+    strand's bases 0-4 -- mapped back by the function the table is stored by."""
     words = np.ascontiguousarray(words, dtype=np.uint32)
     if words.ndim != 2 or words.shape[1] != 3:
         raise ValueError("words must be n x 3")

@@ -992,14 +992,16 @@ DREPHIP_EXPORT int drephip_prefilter_eval(const uint64_t *q1, const uint64_t *q2
 }
 
 // The sketch kernel's canonical-strand cut on the host (canon.h: the inline
-// functions k_sketch_hash21 calls), for tests/test_sketch_canon.py
+// functions k_sketch_hash21 calls), for tests/test_sketch_canon.py and
+// tests/test_sketch_tail.py.  The cut yields the tail table's index; the
+// natural tail index comes back through the map the table was stored by
 DREPHIP_EXPORT int drephip_canon_eval(const uint32_t *words, uint64_t n, uint32_t r, uint32_t *hi, uint32_t *tail) {
     if (r > 15 || (n && (!words || !hi || !tail))) { set_error("bad argument"); return DREPHIP_ERR_ARG; }
     for (uint64_t i = 0; i < n; i++) {
         const uint32_t *f = words + 3 * i;           // F[m-2], F[m-1], F[m]
         uint32_t toff;
-        canon_cut(~f[0], ~f[1], ~f[2], rev_fields16(f[0]), rev_fields16(f[1]), rev_fields16(f[2]), (int)r, hi[i], toff);
-        tail[i] = toff >> 3;
+        canon_cut(~f[1], ~f[2], rev_fields16(f[0]), rev_fields16(f[1]), rev_fields16(f[2]), (int)r, hi[i], toff);
+        tail[i] = tail_index_of_head(toff >> 3);
     }
     return DREPHIP_OK;
 }

@@ -8,7 +8,7 @@
 //     top bits, i.e. it is the reverse complement read MSB-first;
 //   R[j] = F[j] with its 16 fields reversed (rev_fields16): a big-endian cut of
 //     R starting at base q-20 is the forward k-mer MSB-first.
-// For the window end q = 16m + r the kernel holds NF[m-2..m] and R[m-2..m].
+// For the window end q = 16m + r the kernel holds NF[m-1..m] and R[m-2..m].
 //
 // What Murmur needs of the canonical 21-mer is its first 16 bases as one word
 // (bases 0-3 in the top byte: four table indices) and bases 16-20 as a 10-bit
@@ -22,17 +22,24 @@
 // whatever the codes: the 64-bit comparison of the two top-aligned k-mers is
 // the 32-bit comparison of their high words, forward <= reverse  <=>  fhi < chi
 // (k odd: a k-mer never equals its reverse complement).  The canonical high
-// word is min(fhi, chi) -- no dependency on the compare, so the four block
-// table reads issue straight from it -- and only the tail waits for the strand
-// bit.
+// word is min(fhi, chi): no compare, no strand bit.
 //
-// Tail.  The forward strand's bases 16-20 are bases q-4..q of R, the reverse
-// strand's are the complements of bases q-16..q-20, bases q-20..q-16 of NF read
-// MSB-first: a 10-bit field of one code word for r >= 4 and of two for r < 4
-// (both strands straddle at the same residues).  The field is moved to bits
-// 3..12 -- the byte offset of an 8-byte table entry -- by one shift or one
-// v_alignbit_b32, with junk above and below; one select on the strand bit and
-// one AND with 0x1FF8 finish it.
+// Tail.  The canonical strand's bases 16-20 stand in the high word of the
+// strand that lost.  Let f[0..20] be the forward k-mer and r[i] = 3 - f[20-i]
+// its reverse complement.  The top five bases of chi are r[0..4] =
+// 3-f[20], 3-f[19], .., 3-f[16]: the forward tail f[16..20], reversed and
+// complemented.  The top five bases of fhi are f[0..4], and the reverse tail
+// is r[16+j] = 3 - f[4-j]: again the tail, reversed and complemented, by the
+// same map.  Whichever strand wins, the other's high word is max(fhi, chi)
+// (fhi != chi), so with u = the top 10 bits of max(fhi, chi) the canonical
+// tail is t[16+j] = 3 - u_field[4-j], as a number (base 16 on top)
+//     y = rev5(~u & 0x3FF)          (rev5: the five 2-bit fields reversed)
+// = tail_index_of_head(u).  Complement and field reversal commute and each is
+// its own inverse, so u -> y is an involution, hence a bijection of 0..1023.
+// The kernel's tail table is stored permuted -- the entry of tail y at index
+// tail_index_of_head(y), so index u holds the entry of tail y(u) -- and the
+// tail offset is u << 3 = (max(fhi, chi) >> 19) & 0x1FF8: one v_max_u32, one
+// shift, one AND, the same at every residue, reading no further code word.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -56,32 +63,28 @@ __host__ __device__ __forceinline__ uint32_t rev_fields16(uint32_t x) {     // r
 
 constexpr uint32_t kTailOffMask = 0x1FF8u;      // 10-bit tail index << 3
 
-// x's 10-bit field at bits at..at+9, moved to bits 3..12 (junk around it)
-__host__ __device__ __forceinline__ uint32_t field_to_3(uint32_t x, int at) {
-    return at >= 3 ? x >> (at - 3) : x << (3 - at);
+// The canonical tail (bases 16-20, base 16 on top) from u = bases 0-4 of the
+// other strand (base 0 on top), and back: rev5(~u & 0x3FF), an involution.
+// The tail table's index map (sketch.hip build_tables) and the host
+// evaluator's (api.cpp drephip_canon_eval).
+__host__ __device__ __forceinline__ uint32_t tail_index_of_head(uint32_t u) {
+    return rev_fields16(~u & 0x3FFu) >> 22;      // fields 0-4 land in fields 15-11
 }
 
 // Canonical k-mer of window end q = 16m + r, 0 <= r <= 15 (a constant in the
-// kernel's unrolled body), from nf0..nf2 = NF[m-2..m] and r0..r2 = R[m-2..m]:
-// hi = its bases 0-15 MSB-first, toff = 8 * (its bases 16-20 as a 10-bit
-// number, base 16 on top).
-__host__ __device__ __forceinline__ void canon_cut(uint32_t nf0, uint32_t nf1, uint32_t nf2, uint32_t r0,
-                                                   uint32_t r1, uint32_t r2, int r, uint32_t &hi, uint32_t &toff) {
+// kernel's unrolled body), from nf1, nf2 = NF[m-1..m] and r0..r2 = R[m-2..m]:
+// hi = its bases 0-15 MSB-first, toff = 8 * (bases 0-4 of the other strand as
+// a 10-bit number, base 0 on top) -- the byte offset of the canonical tail's
+// entry in the permuted tail table; its bases 16-20 are
+// tail_index_of_head(toff >> 3).
+__host__ __device__ __forceinline__ void canon_cut(uint32_t nf1, uint32_t nf2, uint32_t r0, uint32_t r1,
+                                                   uint32_t r2, int r, uint32_t &hi, uint32_t &toff) {
     // reverse strand: bases q..q-15 complemented
     const uint32_t chi = r == 15 ? nf2 : alignbit32(nf2, nf1, 2 * (r + 1));
     // forward strand: bases q-20..q-5; q-20 is field r+12 of word m-2 or field r-4 of word m-1
     const uint32_t fhi = r < 4 ? alignbit32(r0, r1, 32 - 2 * (r + 12)) : r == 4 ? r1 : alignbit32(r1, r2, 32 - 2 * (r - 4));
-    uint32_t ft, ct;
-    if (r < 4) {
-        // forward: bits 30-2r..39-2r of r1:r2; reverse: bits 24+2r..33+2r of nf1:nf0
-        ft = alignbit32(r1, r2, 27 - 2 * r);
-        ct = alignbit32(nf1, nf0, 21 + 2 * r);
-    } else {
-        ft = field_to_3(r2, 30 - 2 * r);         // base q at bits 30-2r of R[m]
-        ct = field_to_3(nf1, 2 * (r - 4));       // base q-20 at field r-4 of NF[m-1]
-    }
     hi = fhi < chi ? fhi : chi;
-    toff = (fhi < chi ? ft : ct) & kTailOffMask;
+    toff = ((fhi < chi ? chi : fhi) >> 19) & kTailOffMask;
 }
 
 }  // namespace drephip

@@ -96,8 +96,8 @@ constexpr uint32_t kStage = DREPHIP_SK_STAGE;
 // first 16 bases of the forward and of the reverse-complement k-mer are cut
 // out of the 2-bit code stream with one v_alignbit_b32 each, the smaller is
 // the canonical high word (the high words always differ and decide the
-// strand), the 5-base tail index is cut from the code words of the chosen
-// strand (canon.h, with the streams and the proof), and the parts of
+// strand), the larger holds the canonical tail's table index in its top 10
+// bits (canon.h, with the streams and the proofs), and the parts of
 // MurmurHash3_x64_128 (seed 42, h1) that depend only on a few bases come from
 // per-workgroup LDS tables.
 //
@@ -112,7 +112,8 @@ constexpr uint32_t kStage = DREPHIP_SK_STAGE;
 // one v_mad_u64_u32 plus a high-word fix.  Likewise for k2:
 //     rotl(X, 33) * c1 = hi(X) * (2 c1) + TT2,
 //     TT2 = ((lo(X) & 0x7fffffff) << 33) * c1 + (lo(X) >> 31) * c1.
-// The tail is one table entry, rotl31(k3 c1) c2 ^ 21 (Murmur's h1 ^= len).
+// The tail is one table entry, rotl31(k3 c1) c2 ^ 21 (Murmur's h1 ^= len),
+// stored at the index the other strand's bases 0-4 give (tail_index_of_head).
 //
 // Cost model (measured, profiles/r02_sketch_ab.json): the loop is VALU-issue
 // bound -- its time follows the VALU instruction count (a layout with 17 %
@@ -139,7 +140,7 @@ struct SketchTablesQ {
     u32x4 e2[256];        // {lo(TT2), hi(TT2), hi(A03 c2), hi(A03 c2) hi(2 c1)}     by bases 8-11
     u32x2 b1[256];        // {A47 lo(c1), A47 lo(c1) << 31}                         by bases 4-7
     u32x2 b2[256];        // {A47 lo(c2), A47 lo(c2) hi(2 c1)}                      by bases 12-15
-    uint64_t t3[1024];    // tail, by bases 16-20
+    uint64_t t3[1024];    // tail (bases 16-20), by the other strand's bases 0-4
 };
 
 __device__ __forceinline__ uint32_t ascii4(uint32_t x) {      // 4 bases, base 0 in bits 6-7
@@ -165,9 +166,10 @@ __device__ void build_tables(SketchTablesQ &tb, uint32_t tid, uint32_t nthreads)
         tb.b2[x] = u32x2{m2, m2 * d1hi};
     }
     for (uint32_t y = tid; y < 1024; y += nthreads) {
-        // bases 16..19 = bits 9..2, base 20 = bits 1..0
+        // bases 16..19 = bits 9..2, base 20 = bits 1..0; stored where the losing
+        // strand's high word points (canon.h: an involution, so every slot is written once)
         const uint64_t k3 = (uint64_t)ascii4(y >> 2) | ((uint64_t)ascii4((y & 3u) << 6) & 0xffu) << 32;
-        tb.t3[y] = (rotl64_ab(k3 * c1, 31) * c2) ^ 21u;
+        tb.t3[tail_index_of_head(y)] = (rotl64_ab(k3 * c1, 31) * c2) ^ 21u;
     }
 }
 
@@ -332,9 +334,9 @@ __global__ __launch_bounds__(kTile / LANE, DREPHIP_SK_MINW) void k_sketch_hash21
     auto ld = [&](int j) -> uint32_t {               // word m0 + j, m0 = the lane's first window end / 16
         return __builtin_amdgcn_raw_buffer_load_b32(crs, lane_off, (uint32_t)__builtin_amdgcn_readfirstlane(j + 2) * 4u, 0);
     };
-    // registers: F words m-2..m (complemented), R words m-2..m and, one chunk ahead, m+1
-    uint32_t nf0 = ~ld(-2), nf1 = ~ld(-1), nf2 = ~ld(0);
-    uint32_t r0 = rev_fields16(~nf0), r1 = rev_fields16(~nf1), r2 = rev_fields16(~nf2);
+    // registers: F words m-1..m (complemented), R words m-2..m and, one chunk ahead, m+1
+    uint32_t nf1 = ~ld(-1), nf2 = ~ld(0);
+    uint32_t r0 = rev_fields16(ld(-2)), r1 = rev_fields16(~nf1), r2 = rev_fields16(~nf2);
     uint32_t f3 = ld(1);                             // raw F[m+1]
     uint32_t r3 = rev_fields16(f3);
     uint32_t fnext = ld(2);
@@ -355,7 +357,7 @@ __global__ __launch_bounds__(kTile / LANE, DREPHIP_SK_MINW) void k_sketch_hash21
         if (wi + 1 < NCH && (wi & 1)) vcur = vw[2 + (wi >> 1)];
         vhist = (vhist >> 16) | ((uint64_t)vbits << 48);
         // canonical k-mer of window end q = 16m + r: high word and tail offset (canon.h)
-        auto canon = [&](int r, uint32_t &hi, uint32_t &toff) { canon_cut(nf0, nf1, nf2, r0, r1, r2, r, hi, toff); };
+        auto canon = [&](int r, uint32_t &hi, uint32_t &toff) { canon_cut(nf1, nf2, r0, r1, r2, r, hi, toff); };
 #pragma unroll
         for (int b0 = 0; b0 < 16; b0 += BATCH) {
             uint64_t p1[BATCH], p2[BATCH];
@@ -392,7 +394,7 @@ __global__ __launch_bounds__(kTile / LANE, DREPHIP_SK_MINW) void k_sketch_hash21
             }
         }
         // slide one code word
-        nf0 = nf1; nf1 = nf2; nf2 = ~f3;
+        nf1 = nf2; nf2 = ~f3;
         r0 = r1; r1 = r2; r2 = r3;
         f3 = fnext;
         r3 = rev_fields16(f3);

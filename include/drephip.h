@@ -192,7 +192,10 @@ int drephip_prefilter_eval(const uint64_t *q1, const uint64_t *q2, uint64_t n, u
  * r (0..15) names the window end q = 16m + r, the 21-mer of bases q-20..q.
  * For each triple: hi[i] = bases 0-15 of the canonical k-mer (the smaller of
  * the k-mer and its reverse complement in ASCII order), base 0 in the top two
- * bits; tail[i] = its bases 16-20 as a 10-bit number, base 16 on top. */
+ * bits; tail[i] = its bases 16-20 as a 10-bit number, base 16 on top.  The
+ * kernel indexes its tail table by the top five bases of the other strand's
+ * high word; the natural index returned here is that index taken through
+ * tail_index_of_head, the map the table is stored by. */
 int drephip_canon_eval(const uint32_t *words, uint64_t n, uint32_t r, uint32_t *hi, uint32_t *tail);
 
 /* ---------------------------------------------------------------- dist

@@ -40,7 +40,7 @@ CLASS = {
     "v_lshlrev_b32_e32": "v_lshlrev_b32_e32", "v_lshlrev_b32_sdwa": "v_lshlrev_b32_sdwa (sgpr shift, byte select)",
     "v_or_b32_sdwa": "v_lshlrev_b32_sdwa (sgpr shift, byte select)", "v_lshlrev_b64": "v_lshlrev_b64",
     "v_lshrrev_b32_e32": "v_lshrrev_b32_e32", "v_lshrrev_b64": "v_lshrrev_b64", "v_mad_u64_u32": "v_mad_u64_u32",
-    "v_min_u32_e32": "v_min_u32_e32", "v_mov_b32_e32": "v_mov_b32_e32", "v_mov_b64_e32": "v_mov_b64_e32",
+    "v_min_u32_e32": "v_min_u32_e32", "v_max_u32_e32": "v_min_u32_e32", "v_mov_b32_e32": "v_mov_b32_e32", "v_mov_b64_e32": "v_mov_b64_e32",
     "v_mul_hi_u32": "v_mul_hi_u32", "v_mul_lo_u32": "v_mul_lo_u32", "v_not_b32_e32": "v_not_b32_e32",
     "v_or_b32_e32": "v_or_b32_e32", "v_perm_b32": "v_perm_b32",
 }
