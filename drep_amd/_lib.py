@@ -62,6 +62,12 @@ SIGNATURES = {
                                             C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "drephip_last_ingest_phases": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                              C.POINTER(C.c_uint32)]),
+    "drephip_text_tile_bytes": (C.c_uint32, []),
+    "drephip_fasta_pack_device": (C.c_int, [vp, vp, u64p, C.c_uint32, u64p, u64p, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "drephip_set_ingest_path": (C.c_int, [vp, C.c_int]),
+    "drephip_get_ingest_path": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "drephip_last_ingest_paths": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint64)]),
     "drephip_sketch_device": (C.c_int, [vp, vp, vp, u64p, u64p, u64p, C.c_uint32, vp, vp, vp]),
     "drephip_sketch_device_async": (C.c_int, [vp, vp, vp, u64p, u64p, u64p, C.c_uint32, vp, vp, vp]),
     "drephip_sketch_wait": (C.c_int, [vp, C.POINTER(C.c_int)]),
@@ -211,6 +217,31 @@ def max_sketch() -> int:
 
 def tile_bases() -> int:
     return int(lib().drephip_tile_bases())
+
+
+def text_tile_bytes() -> int:
+    """Bytes of FASTA text per tile of the device ingest kernels (a power of two)."""
+    return int(lib().drephip_text_tile_bytes())
+
+
+def text_layout(sizes: Sequence[int]) -> Tuple[np.ndarray, np.ndarray]:
+    """Where files of the given byte sizes go in a device text buffer for
+    Context.fasta_pack_device: (starts, text_off).  File f is written at
+    starts[f] (16-byte aligned); text_off (n + 1 entries) is what the call
+    takes: file f ends at text_off[f + 1] and the next one starts at the
+    16-byte boundary at or after it.  The buffer holds text_off[-1] bytes."""
+    starts = np.zeros(len(sizes), np.uint64)
+    off = np.zeros(len(sizes) + 1, np.uint64)
+    at = 0
+    for f, sz in enumerate(sizes):
+        at = (at + 15) // 16 * 16
+        starts[f] = at
+        at += int(sz)
+        off[f + 1] = at
+    return starts, off
+
+
+INGEST_PATHS = {"host": 0, "device": 1}
 
 
 def padded_bases(rec_len: Sequence[int]) -> int:
@@ -526,6 +557,56 @@ class Context:
         check(lib().drephip_sketch_files(self._h, arr, n, int(threads), hashes.reshape(-1), nhash, length),
               "drephip_sketch_files")
         return hashes, nhash, length
+
+    def set_ingest_path(self, path: str) -> None:
+        """Who parses and packs the files of sketch_files: "host" (worker
+        threads; the default) or "device" (kernels on the raw text)."""
+        if path not in INGEST_PATHS:
+            raise ValueError("ingest must be 'host' or 'device', got %r" % (path,))
+        check(lib().drephip_set_ingest_path(self._h, INGEST_PATHS[path]), "drephip_set_ingest_path")
+
+    @property
+    def ingest_path(self) -> str:
+        v = C.c_int(0)
+        check(lib().drephip_get_ingest_path(self._h, C.byref(v)), "drephip_get_ingest_path")
+        return {0: "host", 1: "device"}[v.value]
+
+    def ingest_paths(self) -> dict:
+        """{path, device_files, host_files, text_bytes}: the context's ingest
+        path, and for the last sketch_files call the files the device packed,
+        the files that took the host reader and the text bytes copied."""
+        d, h, t = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        check(lib().drephip_last_ingest_paths(self._h, C.byref(d), C.byref(h), C.byref(t)),
+              "drephip_last_ingest_paths")
+        return {"path": self.ingest_path, "device_files": d.value, "host_files": h.value, "text_bytes": t.value}
+
+    def fasta_pack_device(self, text, text_off, base_off, cap_bases, d_codes, d_valid,
+                          stream: Optional[int] = None) -> dict:
+        """drephip_fasta_pack_device: parse and pack FASTA text that is in
+        device memory.  `text`: a torch.uint8 CUDA tensor or a device pointer;
+        `text_off`: n + 1 offsets (see text_layout); `base_off` / `cap_bases`:
+        each file's region in `d_codes` / `d_valid` (torch tensors or device
+        pointers).  Returns numpy arrays {length, padded, n_records, n_kmers,
+        status} (status 0 packed, 1 needs the host reader, 2 region too small)."""
+        def ptr(x):
+            return int(x.data_ptr()) if hasattr(x, "data_ptr") else (None if x is None else int(x))
+        text_off = np.ascontiguousarray(text_off, dtype=np.uint64)
+        base_off = np.ascontiguousarray(base_off, dtype=np.uint64)
+        cap_bases = np.ascontiguousarray(cap_bases, dtype=np.uint64)
+        n = len(base_off)
+        if len(text_off) != n + 1 or len(cap_bases) != n:
+            raise ValueError("text_off must hold n + 1 and cap_bases n entries")
+        m = max(n, 1)
+        out = {"length": np.zeros(m, np.uint64), "padded": np.zeros(m, np.uint64),
+               "n_records": np.zeros(m, np.uint32), "n_kmers": np.zeros(m, np.uint64),
+               "status": np.zeros(m, np.uint8)}
+        z = np.zeros(1, np.uint64)
+        check(lib().drephip_fasta_pack_device(self._h, ptr(text), text_off, n, base_off if n else z,
+                                              cap_bases if n else z, ptr(d_codes), ptr(d_valid),
+                                              out["length"].ctypes.data, out["padded"].ctypes.data,
+                                              out["n_records"].ctypes.data, out["n_kmers"].ctypes.data,
+                                              out["status"].ctypes.data, stream), "drephip_fasta_pack_device")
+        return {k: v[:n] for k, v in out.items()}
 
     def ingest_stats(self):
         """{produce_s, gpu_s, wall_s, batches} of the last sketch_files call."""

@@ -7,6 +7,9 @@
 #include "prefilter.h"
 #include "../../include/drephip.h"
 
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -136,7 +139,7 @@ static int refuse_if_pending(drephip_ctx *ctx) {
     return DREPHIP_ERR_ARG;
 }
 
-DREPHIP_EXPORT int drephip_version(void) { return 200; }
+DREPHIP_EXPORT int drephip_version(void) { return 300; }
 
 #ifndef DREPHIP_SRC_DIGEST
 #define DREPHIP_SRC_DIGEST "unknown"
@@ -184,6 +187,8 @@ DREPHIP_EXPORT int drephip_create(int device, int k, uint32_t s, uint32_t seed, 
     if (const char *lp = std::getenv("DREPHIP_LINK_PATH"))      // default linkage path (tests, A/B runs)
         c->link_path = !strcmp(lp, "dense") ? DREPHIP_LINK_PATH_DENSE : !strcmp(lp, "sparse") ? DREPHIP_LINK_PATH_SPARSE
                                                                                                 : DREPHIP_LINK_PATH_AUTO;
+    if (const char *ip = std::getenv("DREPHIP_INGEST"))         // default ingest path of drephip_sketch_files
+        c->ingest_path = !strcmp(ip, "device") ? DREPHIP_INGEST_DEVICE : DREPHIP_INGEST_HOST;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete c; set_error(hipGetErrorString(e)); return DREPHIP_ERR_HIP; }
     *out = c;
@@ -514,6 +519,320 @@ static void produce_batch(const char *const *paths, uint32_t g0, uint32_t n_geno
     B.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// ------------------------------------------------------------ device ingest
+// One file read and packed by the host code into buffers of its own (the
+// device path's gzip and FASTQ files), at base 0.
+struct HostPacked {
+    std::vector<uint32_t> codes, valid;
+    uint64_t pad = 0, nk = 0, length = 0;
+};
+static int host_pack_file(const char *path, int k, Genome &g, HostPacked &hp, double *t_read, double *t_pack) {
+    const auto r0 = std::chrono::steady_clock::now();
+    const int rr = read_fasta(path, g);
+    const auto r1 = std::chrono::steady_clock::now();
+    *t_read += std::chrono::duration<double>(r1 - r0).count();
+    if (rr) return DREPHIP_ERR_IO;
+    const uint32_t nr = (uint32_t)g.rec_len.size();
+    hp.pad = padded_span(genome_span(g.rec_len.data(), nr));
+    hp.length = g.length;
+    hp.codes.assign(hp.pad / 16, 0);
+    hp.valid.assign(hp.pad / 32, 0);
+    hp.nk = pack_records(g.seq.data(), g.rec_len.data(), nr, k, hp.codes.data(), hp.valid.data(), 0);
+    *t_pack += std::chrono::duration<double>(std::chrono::steady_clock::now() - r1).count();
+    return DREPHIP_OK;
+}
+
+// One batch of the device path: the plain files' bytes in a pinned text
+// buffer (16-byte aligned starts), the gzip files packed by the host code.
+struct TextBatch {
+    uint32_t g0 = 0, n = 0;
+    std::vector<uint64_t> off, reserved;        // region of each file (bases)
+    std::vector<uint64_t> text_beg, text_end;   // plain files: their bytes in the text buffer
+    std::vector<char> host;                     // 1: packed by the host code (hp)
+    std::vector<HostPacked> hp;
+    uint64_t bases = 0, text_bytes = 0, text_span = 0;
+    int err = 0;
+    std::string msg;
+    double seconds = 0, read_thread_s = 0, pack_thread_s = 0;
+};
+
+// One look at a file: its size, whether it is gzip, and the upper bound on its
+// bases that estimate_bases gives (the same rule, from the same open).
+// false: it cannot be opened.
+static bool probe_file(const char *path, uint64_t *size, bool *gz, uint64_t *est) {
+    FILE *fp = fopen(path, "rb");
+    if (!fp) return false;
+    uint8_t magic[2] = {0, 0};
+    const size_t got = fread(magic, 1, 2, fp);
+    fseek(fp, 0, SEEK_END);
+    const long sz = ftell(fp);
+    *size = sz > 0 ? (uint64_t)sz : 0;
+    *gz = got == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+    *est = *size;
+    if (*gz && sz >= 18) {
+        uint8_t t[4];
+        fseek(fp, -4, SEEK_END);
+        if (fread(t, 1, 4, fp) == 4) {
+            const uint64_t isize = (uint64_t)t[0] | (uint64_t)t[1] << 8 | (uint64_t)t[2] << 16 | (uint64_t)t[3] << 24;
+            *est = isize >= (uint64_t)sz ? isize : 4 * (uint64_t)sz;
+        }
+    }
+    fclose(fp);
+    return true;
+}
+
+// The device path's producer: the same choice of files and regions as
+// produce_batch (one probe per file gives its estimate, size and kind); then,
+// on `threads` workers, each plain file's bytes go into the pinned text buffer
+// with one pread, unparsed, and each gzip file through the host reader and
+// packer.  A plain file whose size is no longer the probed one takes the host
+// reader too, which reads it whole.
+static void produce_text_batch(const char *const *paths, uint32_t g0, uint32_t n_genomes, int threads, int k,
+                               uint64_t target, PinnedText &slot, TextBatch &B, int device) {
+    const auto t0 = std::chrono::steady_clock::now();
+    (void)hipSetDevice(device);
+    B = TextBatch();
+    B.g0 = g0;
+    uint64_t est_total = 0, cur = kTile, tcur = 0;
+    uint32_t g1 = g0;
+    while (g1 < n_genomes && (g1 == g0 || est_total < target)) {
+        uint64_t size = 0, est = 0;
+        bool gz = false;
+        if (!probe_file(paths[g1], &size, &gz, &est)) {
+            B.n = g1 - g0 + 1;
+            B.err = DREPHIP_ERR_IO; B.msg = std::string("cannot open ") + paths[g1]; return;
+        }
+        B.reserved.push_back(padded_span(est));
+        B.off.push_back(cur);
+        cur += B.reserved.back();
+        B.host.push_back(gz ? 1 : 0);
+        B.text_beg.push_back(tcur);
+        B.text_end.push_back(gz ? tcur : tcur + size);
+        if (!gz) tcur += round_up(size, 16);
+        est_total += est;
+        g1++;
+    }
+    const uint32_t n = g1 - g0;
+    B.n = n;
+    B.hp.resize(n);
+    B.bases = cur;
+    B.text_span = tcur;
+    if (slot.reserve(std::max<uint64_t>(tcur, 16))) {
+        B.err = DREPHIP_ERR_NOMEM; B.msg = "hipHostMalloc of the pinned text batch failed"; return;
+    }
+    std::vector<int> err(n, 0);
+    std::vector<std::string> msg(n);
+    const uint32_t nw = (uint32_t)std::max(1, threads > 0 ? threads : (int)std::thread::hardware_concurrency());
+    std::vector<Genome> work(nw);
+    std::vector<double> t_read(nw, 0.0), t_pack(nw, 0.0);
+    std::atomic<uint32_t> next(0);
+    auto worker = [&](uint32_t w) {
+        for (uint32_t i = next++; i < n; i = next++) {
+            const char *path = paths[g0 + i];
+            if (!B.host[i]) {
+                const auto r0 = std::chrono::steady_clock::now();
+                const int fd = open(path, O_RDONLY);
+                if (fd < 0) { err[i] = DREPHIP_ERR_IO; msg[i] = std::string("cannot open ") + path; continue; }
+                const uint64_t want = B.text_end[i] - B.text_beg[i];
+                struct stat sb;
+                bool same = fstat(fd, &sb) == 0 && (uint64_t)sb.st_size == want;
+                uint64_t got = 0;
+                bool bad = false;
+                while (same && got < want) {           // one pread, repeated only when it comes back short
+                    const ssize_t r = pread(fd, slot.ptr + B.text_beg[i] + got, want - got, (off_t)got);
+                    if (r < 0) { bad = true; break; }
+                    if (r == 0) { same = false; break; }
+                    got += (uint64_t)r;
+                }
+                close(fd);
+                if (bad) { err[i] = DREPHIP_ERR_IO; msg[i] = std::string("read error in ") + path; continue; }
+                t_read[w] += std::chrono::duration<double>(std::chrono::steady_clock::now() - r0).count();
+                if (same) continue;
+                B.host[i] = 1;                         // the file changed since the probe
+                B.text_end[i] = B.text_beg[i];
+            }
+            const int rc = host_pack_file(path, k, work[w], B.hp[i], &t_read[w], &t_pack[w]);
+            if (rc) { err[i] = rc; msg[i] = drephip_last_error(); }
+        }
+    };
+    const uint32_t nt = std::min(nw, n);
+    std::vector<std::thread> pool;
+    for (uint32_t w = 1; w < nt; w++) pool.emplace_back(worker, w);
+    worker(0);
+    for (auto &th : pool) th.join();
+    for (uint32_t i = 0; i < n; i++)
+        if (err[i]) { B.err = err[i]; B.msg = msg[i]; return; }
+    for (uint32_t w = 0; w < nw; w++) { B.read_thread_s += t_read[w]; B.pack_thread_s += t_pack[w]; }
+    for (uint32_t i = 0; i < n; i++) B.text_bytes += B.text_end[i] - B.text_beg[i];
+    B.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The device path's consumer: text to the device, pack kernels, the host
+// reader for the files the kernels hand back, then the device-resident sketch.
+// A host-packed file (gzip, FASTQ, or a defensive status 2) is copied over its
+// region, which is zeroed whole first: the slack behind a genome's padded span
+// is read by the sketch of the genome that follows and must not keep what an
+// earlier batch left in the scratch.  One whose span outgrew its region goes to
+// the end of the batch (its old region zeroed all the same).
+static int consume_text_batch(drephip_ctx *ctx, const char *const *paths, int threads, TextBatch &B,
+                              const PinnedText &slot, uint64_t *hashes_out, uint32_t *nhash_out,
+                              uint64_t *length_out) {
+    const uint32_t n = B.n;
+    hipStream_t st = ctx->stream;
+    std::vector<uint64_t> pad(n, 0), nk(n, 0), length(n, 0), off(B.off);
+    uint32_t moved = 0, device_files = 0, host_files = 0;
+    uint64_t end = B.bases;
+    for (uint32_t i = 0; i < n; i++)
+        if (B.host[i] && B.hp[i].pad > B.reserved[i]) { off[i] = end; end += B.hp[i].pad; moved++; }
+    uint8_t *d_text;
+    uint32_t *d_codes, *d_valid, *d_nhash;
+    uint64_t *d_hashes;
+    int rc;
+    if ((rc = scratch(ctx, "in_text", std::max<uint64_t>(B.text_span, 16), (void **)&d_text))) return rc;
+    if ((rc = scratch(ctx, "in_codes", end / 16 * 4, (void **)&d_codes))) return rc;
+    if ((rc = scratch(ctx, "in_valid", end / 32 * 4, (void **)&d_valid))) return rc;
+    if ((rc = scratch(ctx, "out_hashes", (uint64_t)n * ctx->s * 8, (void **)&d_hashes))) return rc;
+    if ((rc = scratch(ctx, "out_nhash", n * 4ull, (void **)&d_nhash))) return rc;
+    if (B.text_span) HIPC(hipMemcpyAsync(d_text, slot.ptr, B.text_span, hipMemcpyHostToDevice, st));
+    HIPC(hipMemsetAsync(d_codes, 0, kTile / 16 * 4, st));
+    HIPC(hipMemsetAsync(d_valid, 0, kTile / 32 * 4, st));
+    for (uint32_t i = 0; i < n; i++) {                   // the host-packed files' regions (the pack call zeroes the others)
+        if (!B.host[i]) continue;
+        HIPC(hipMemsetAsync(d_codes + B.off[i] / 16, 0, B.reserved[i] / 16 * 4, st));
+        HIPC(hipMemsetAsync(d_valid + B.off[i] / 32, 0, B.reserved[i] / 32 * 4, st));
+    }
+    std::vector<uint32_t> dev;                           // the plain files
+    for (uint32_t i = 0; i < n; i++) if (!B.host[i]) dev.push_back(i);
+    std::vector<uint32_t> back;                          // handed back to the host reader
+    if (!dev.empty()) {
+        const uint32_t m = (uint32_t)dev.size();
+        std::vector<uint64_t> tb(m), te(m), bo(m), cp(m), ln(m), pd(m), kk(m);
+        std::vector<uint32_t> nr(m);
+        std::vector<uint8_t> stt(m);
+        for (uint32_t j = 0; j < m; j++) {
+            tb[j] = B.text_beg[dev[j]]; te[j] = B.text_end[dev[j]];
+            bo[j] = B.off[dev[j]]; cp[j] = B.reserved[dev[j]];
+        }
+        rc = fasta_pack_device_impl(ctx, d_text, tb.data(), te.data(), m, bo.data(), cp.data(), d_codes, d_valid, ln.data(),
+                                    pd.data(), nr.data(), kk.data(), stt.data(), st);
+        if (rc) return rc;
+        for (uint32_t j = 0; j < m; j++) {
+            const uint32_t i = dev[j];
+            if (stt[j] == 0) { length[i] = ln[j]; pad[i] = pd[j]; nk[i] = kk[j]; device_files++; }
+            else back.push_back(i);
+        }
+    }
+    if (!back.empty()) {
+        std::vector<int> err(back.size(), 0);
+        std::vector<std::string> msg(back.size());
+        std::vector<double> tr(back.size(), 0.0), tp(back.size(), 0.0);
+        parallel_for((uint32_t)back.size(), threads, [&](uint32_t j) {
+            Genome g;
+            err[j] = host_pack_file(paths[B.g0 + back[j]], ctx->k, g, B.hp[back[j]], &tr[j], &tp[j]);
+            if (err[j]) msg[j] = drephip_last_error();
+        });
+        bool again = false;
+        for (size_t j = 0; j < back.size(); j++) {
+            if (err[j]) { set_error(msg[j]); return err[j]; }
+            ctx->ingest.read_thread_s += tr[j];
+            ctx->ingest.pack_thread_s += tp[j];
+            B.host[back[j]] = 1;
+            again |= B.hp[back[j]].pad > B.reserved[back[j]];
+        }
+        // A handed-back file that outgrew its region needs room behind the batch, as
+        // a gzip file does: start over with it among the host-packed files (the
+        // buffers may move).  A plain file's span never exceeds its size's, so
+        // this is a defence only.
+        if (again) return consume_text_batch(ctx, paths, threads, B, slot, hashes_out, nhash_out, length_out);
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        if (!B.host[i]) continue;
+        const HostPacked &hp = B.hp[i];
+        HIPC(hipMemcpyAsync(d_codes + off[i] / 16, hp.codes.data(), hp.pad / 16 * 4, hipMemcpyHostToDevice, st));
+        HIPC(hipMemcpyAsync(d_valid + off[i] / 32, hp.valid.data(), hp.pad / 32 * 4, hipMemcpyHostToDevice, st));
+        length[i] = hp.length; pad[i] = hp.pad; nk[i] = hp.nk;
+        host_files++;
+    }
+    if (length_out) std::copy(length.begin(), length.end(), length_out + B.g0);
+    timing_begin(ctx);
+    rc = sketch_device_impl(ctx, d_codes, d_valid, off.data(), pad.data(), nk.data(), n, d_hashes, d_nhash, st);
+    if (rc) return rc;
+    timing_collect(ctx);
+    HIPC(hipMemcpyAsync(hashes_out + (uint64_t)B.g0 * ctx->s, d_hashes, (uint64_t)n * ctx->s * 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(nhash_out + B.g0, d_nhash, n * 4ull, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    ctx->ingest_paths.text_bytes += B.text_bytes;
+    ctx->ingest_paths.device_files += device_files;
+    ctx->ingest_paths.host_files += host_files;
+    ctx->ingest.overflow += moved;
+    return DREPHIP_OK;
+}
+
+// drephip_sketch_files on the device path: the same double-buffered producer /
+// consumer as the host path below, over text batches.
+static int sketch_files_device(drephip_ctx *ctx, const char *const *paths, uint32_t n_genomes, int threads,
+                               uint64_t *hashes_out, uint32_t *nhash_out, uint64_t *length_out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t target = ingest_batch_bases();
+    PinnedText *slots = ctx->ingest_text;
+    TextBatch B[2];
+    const int k = ctx->k;
+    std::mutex mu;
+    std::condition_variable cv;
+    uint32_t produced = 0, consumed = 0;
+    bool stop = false;
+    std::thread producer([&] {
+        uint32_t g = 0;
+        for (uint32_t i = 0; g < n_genomes; i++) {
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return stop || consumed + 2 > i; });
+                if (stop) return;
+            }
+            produce_text_batch(paths, g, n_genomes, threads, k, target, slots[i & 1], B[i & 1], ctx->device);
+            const bool last = B[i & 1].err || g + B[i & 1].n >= n_genomes;
+            g += B[i & 1].n;
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                produced = i + 1;
+            }
+            cv.notify_all();
+            if (last) return;
+        }
+    });
+    int rc = DREPHIP_OK;
+    for (uint32_t b = 0;; b++) {
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return produced > b; });
+        }
+        TextBatch &cur = B[b & 1];
+        if (cur.err) { set_error(cur.msg); rc = cur.err; break; }
+        const bool more = cur.g0 + cur.n < n_genomes;
+        const auto g0 = std::chrono::steady_clock::now();
+        rc = consume_text_batch(ctx, paths, threads, cur, slots[b & 1], hashes_out, nhash_out, length_out);
+        ctx->ingest.gpu_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - g0).count();
+        ctx->ingest.produce_s += cur.seconds;
+        ctx->ingest.read_thread_s += cur.read_thread_s;
+        ctx->ingest.pack_thread_s += cur.pack_thread_s;
+        ctx->ingest.batches++;
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            consumed = b + 1;
+        }
+        cv.notify_all();
+        if (rc || !more) break;
+    }
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        stop = true;
+    }
+    cv.notify_all();
+    producer.join();
+    ctx->ingest.wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
 // Ingest pipeline: one producer thread reads + packs batch i+1 (on `threads`
 // workers, into the other of two pinned buffers) while this thread copies
 // batch i to the GPU and sketches it -- the GPU work hides behind the host
@@ -525,10 +844,14 @@ DREPHIP_EXPORT int drephip_sketch_files(drephip_ctx *ctx, const char *const *pat
                                         uint64_t *length_out) {
     GUARD_CTX(ctx);
     ctx->ingest = IngestStats();
+    ctx->ingest_paths = IngestPaths();
     if (n_genomes == 0) return DREPHIP_OK;
     if (!paths || !hashes_out || !nhash_out) { set_error("null argument"); return DREPHIP_ERR_ARG; }
     int rc;
     if ((rc = refuse_if_pending(ctx))) return rc;
+    if (ctx->ingest_path == DREPHIP_INGEST_DEVICE)
+        return sketch_files_device(ctx, paths, n_genomes, threads, hashes_out, nhash_out, length_out);
+    ctx->ingest_paths.host_files = n_genomes;
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t target = ingest_batch_bases();
     PinnedSlot *slots = ctx->ingest_slots;          // kept across calls: pinned allocation is slow
@@ -609,6 +932,58 @@ DREPHIP_EXPORT int drephip_last_ingest_phases(drephip_ctx *ctx, double *read_thr
     if (read_thread_s) *read_thread_s = ctx->ingest.read_thread_s;
     if (pack_thread_s) *pack_thread_s = ctx->ingest.pack_thread_s;
     if (overflow) *overflow = ctx->ingest.overflow;
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT uint32_t drephip_text_tile_bytes(void) { return text_tile_bytes(); }
+
+DREPHIP_EXPORT int drephip_fasta_pack_device(drephip_ctx *ctx, const uint8_t *d_text, const uint64_t *h_text_off,
+                                             uint32_t n_files, const uint64_t *h_base_off, const uint64_t *h_cap_bases,
+                                             uint32_t *d_codes, uint32_t *d_valid, uint64_t *length_out,
+                                             uint64_t *padded_out, uint32_t *n_records_out, uint64_t *n_kmers_out,
+                                             uint8_t *status_out, void *stream) {
+    GUARD_CTX(ctx);
+    if (n_files == 0) return DREPHIP_OK;
+    if (!d_text || !h_text_off || !h_base_off || !h_cap_bases || !d_codes || !d_valid) {
+        set_error("null argument"); return DREPHIP_ERR_ARG;
+    }
+    if ((uintptr_t)d_text % 16 || h_text_off[0] % 16) {
+        set_error("d_text and text_off[0] must be 16-byte aligned"); return DREPHIP_ERR_ARG;
+    }
+    // file f: from the 16-byte boundary at or after text_off[f] to text_off[f + 1]
+    std::vector<uint64_t> beg(n_files), end(n_files);
+    for (uint32_t f = 0; f < n_files; f++) {
+        if (h_text_off[f + 1] < h_text_off[f]) { set_error("text_off must be non-decreasing"); return DREPHIP_ERR_ARG; }
+        if (h_base_off[f] % kTile || h_cap_bases[f] % kTile) {
+            set_error("base_off and cap_bases must be tile multiples"); return DREPHIP_ERR_ARG;
+        }
+        beg[f] = round_up(h_text_off[f], 16);
+        end[f] = std::max(beg[f], h_text_off[f + 1]);
+    }
+    return fasta_pack_device_impl(ctx, d_text, beg.data(), end.data(), n_files, h_base_off, h_cap_bases, d_codes, d_valid,
+                                  length_out, padded_out, n_records_out, n_kmers_out, status_out,
+                                  pick_stream(ctx, stream));
+}
+
+DREPHIP_EXPORT int drephip_set_ingest_path(drephip_ctx *ctx, int path) {
+    if (!ctx) { set_error("null context"); return DREPHIP_ERR_ARG; }
+    if (path != DREPHIP_INGEST_HOST && path != DREPHIP_INGEST_DEVICE) { set_error("unknown ingest path"); return DREPHIP_ERR_ARG; }
+    ctx->ingest_path = path;
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_get_ingest_path(drephip_ctx *ctx, int *path) {
+    if (!ctx || !path) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    *path = ctx->ingest_path;
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_last_ingest_paths(drephip_ctx *ctx, uint32_t *device_files, uint32_t *host_files,
+                                             uint64_t *text_bytes) {
+    if (!ctx) { set_error("null context"); return DREPHIP_ERR_ARG; }
+    if (device_files) *device_files = ctx->ingest_paths.device_files;
+    if (host_files) *host_files = ctx->ingest_paths.host_files;
+    if (text_bytes) *text_bytes = ctx->ingest_paths.text_bytes;
     return DREPHIP_OK;
 }
 

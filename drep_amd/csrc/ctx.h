@@ -43,6 +43,29 @@ struct PinnedSlot {
     }
 };
 
+// A pinned host buffer of raw FASTA text (the device ingest path).
+struct PinnedText {
+    uint8_t *ptr = nullptr;
+    size_t bytes = 0;
+    PinnedText() = default;
+    PinnedText(const PinnedText &) = delete;
+    PinnedText &operator=(const PinnedText &) = delete;
+    ~PinnedText() { if (ptr) (void)hipHostFree(ptr); }
+    int reserve(size_t b) {
+        if (b <= bytes) return 0;
+        if (ptr) (void)hipHostFree(ptr);
+        ptr = nullptr; bytes = 0;
+        if (hipHostMalloc((void **)&ptr, b, hipHostMallocPortable) != hipSuccess) { ptr = nullptr; return -1; }
+        bytes = b;
+        return 0;
+    }
+};
+
+struct IngestPaths {          // last drephip_sketch_files call: who packed the files
+    uint32_t device_files = 0, host_files = 0;
+    uint64_t text_bytes = 0;  // raw text copied to the device
+};
+
 struct IngestStats {          // last drephip_sketch_files call
     double produce_s = 0;     // host read + pack, summed over batches (producer thread)
     double gpu_s = 0;         // H2D + sketch kernels + D2H, summed over batches (calling thread)
@@ -199,6 +222,9 @@ struct drephip_ctx {
     IngestStats ingest;
     LinkStats link;
     PinnedSlot ingest_slots[2];   // the two pinned batch buffers, kept across calls
+    int ingest_path = 0;          // DREPHIP_INGEST_*: 0 host (default), 1 device
+    IngestPaths ingest_paths;
+    PinnedText ingest_text[2];    // device path: the two pinned text buffers, kept across calls
 };
 
 namespace drephip {
@@ -317,6 +343,18 @@ void sort_and_label(std::vector<double> &Z, uint32_t n);
 // host worker threads of the linkage paths: OMP_NUM_THREADS if set, else the
 // hardware threads, at most 16
 unsigned host_threads();
+
+// Device ingest (ingest_device.hip): FASTA text in device memory (file f at
+// bytes [text_beg[f], text_end[f]), 16-byte aligned starts) parsed and
+// packed into codes/valid at base_off[f], regions of cap[f] bases zeroed first.
+// Per file: length, padded span, records, valid k-mers and status (0 packed, 1
+// needs the host path, 2 region too small).  Blocking.
+uint32_t text_tile_bytes();
+int fasta_pack_device_impl(drephip_ctx *ctx, const uint8_t *d_text, const uint64_t *text_beg,
+                           const uint64_t *text_end, uint32_t n,
+                           const uint64_t *base_off, const uint64_t *cap, uint32_t *d_codes, uint32_t *d_valid,
+                           uint64_t *length_out, uint64_t *padded_out, uint32_t *n_records_out, uint64_t *n_kmers_out,
+                           uint8_t *status_out, hipStream_t st);
 
 // Host ingest (ingest.cpp).
 // std::allocator that leaves new elements uninitialised (resize() without the

@@ -213,12 +213,23 @@ class SketchSet:
     s: int
 
 
+def _check_ingest(kwargs) -> str:
+    """The `ingest` kwarg ('host' by default), or ValueError."""
+    ingest = kwargs.get('ingest', 'host')
+    if ingest not in _lib.INGEST_PATHS:
+        raise ValueError("ingest must be 'host' or 'device', got %r" % (ingest,))
+    return ingest
+
+
 def sketch_genomes(Bdb: pd.DataFrame, data_folder: str, **kwargs) -> SketchSet:
     """The sketch + paste half of all_vs_all_MASH (d_cluster.py:499-567):
     same folders and files (MASH_files/sketches/chunk_<i>/<genome>.msh,
     chunk_all.msh, ALL.msh), sketches cached across runs by file existence
-    (d_cluster.py:541-542), new ones computed on the GPU in one batch."""
+    (d_cluster.py:541-542), new ones computed on the GPU in one batch.
+    `ingest`: 'host' (the default; worker threads parse and pack the FASTA
+    files) or 'device' (the GPU does, from the raw text); same sketches."""
     MASH_s = int(kwargs.get('MASH_sketch', 1000))
+    ingest = _check_ingest(kwargs)
     p = int(kwargs.get('processors', 6))
     groupSize = int(kwargs.get('groupSize', 1000))
     write_sketches = kwargs.get('write_sketches', True)
@@ -274,6 +285,7 @@ def sketch_genomes(Bdb: pd.DataFrame, data_folder: str, **kwargs) -> SketchSet:
             if not shards[k]:
                 return
             with _lib.Context(device=dev, k=MASH_K, s=MASH_s, seed=MASH_SEED) as ctx:
+                ctx.set_ingest_path(ingest)
                 h, nh, ln = ctx.sketch_files([locations[i] for i in shards[k]], threads=threads)
             hashes[shards[k]] = h
             nhash[shards[k]] = nh
@@ -371,10 +383,14 @@ def all_vs_all_MASH(Bdb, data_folder, **kwargs):
             all of them from this process, one host thread per device
         write_sketches: write the .msh files (default True)
         write_table: also write MASH_table.tsv like `mash dist` (default False)
+        ingest: 'host' (default; CPU threads parse and pack the FASTA files) or
+            'device' (the GPU does, from the raw text); the same result.
+            Anything else raises ValueError, also on a dry run
 
     Returns:
         Mdb DataFrame [genome1, genome2, dist, similarity]
     """
+    _check_ingest(kwargs)
     MASH_folder = os.path.join(data_folder, 'MASH_files/')
     if kwargs.get('dry', False):
         table = MASH_folder + 'MASH_table.tsv'

@@ -670,6 +670,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--group-size", type=int, default=1000, help="genomes per sketch chunk folder (dRep groupSize)")
     ap.add_argument("--processors", type=int, default=int(os.environ.get("OMP_NUM_THREADS", "0") or 0),
                     help="host threads for FASTA ingest per rank (0 = all)")
+    ap.add_argument("--ingest", choices=["host", "device"], default="host",
+                    help="who parses and packs the FASTA files: host threads, or the GPU from the raw text")
     ap.add_argument("--sparse", action="store_true",
                     help="list only the pairs that share a hash: no condensed vector, no n x n linkage matrix on any rank")
     a = ap.parse_args(argv)
@@ -684,6 +686,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     else:
         dist.init_process_group(backend, rank=rank, world_size=world)
     ctx = _lib.Context(device=local, k=21, s=a.sketch, seed=42)
+    ctx.set_ingest_path(a.ingest)
     stream = torch.cuda.current_stream(dev).cuda_stream
     from_files = bool(a.bdb or a.files)
     if from_files:

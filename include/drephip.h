@@ -133,6 +133,60 @@ int drephip_last_ingest_stats(drephip_ctx *ctx, double *produce_s, double *gpu_s
 int drephip_last_ingest_phases(drephip_ctx *ctx, double *read_thread_s, double *pack_thread_s,
                                uint32_t *overflow);
 
+/* ---------------------------------------------------------------- device ingest
+ * The kseq parse, the 2-bit pack and the validity bitmap done by kernels on
+ * FASTA text that is already in device memory; bit-exact with
+ * drephip_fasta_pack for every file that holds no FASTQ record.
+ *
+ * Text tile: the kernels cut each file into pieces of this many bytes (a
+ * power of two); exposed so that tests can aim at its edges. */
+uint32_t drephip_text_tile_bytes(void);
+
+/* Device-memory form of drephip_fasta_pack for n_files files at once -- the
+ * same `mash sketch <fasta>` read (drep/d_cluster.py:543-544).  d_text holds
+ * the files' plain text, every file starting on a 16-byte boundary: file f
+ * ends at byte h_text_off[f+1] and starts at the 16-byte boundary at or after
+ * h_text_off[f] (the end of the file before it), so the up to 15 bytes between
+ * two files belong to no file and are never read as text.  d_text and
+ * h_text_off[0] must be 16-byte aligned and h_text_off non-decreasing
+ * (DREPHIP_ERR_ARG otherwise); nothing at or past h_text_off[n_files] is read.
+ * Genome f is packed at base
+ * h_base_off[f] of d_codes/d_valid into a region of h_cap_bases[f] bases, both
+ * multiples of drephip_tile_bases(); the call zeroes each region itself.  A
+ * region of drephip_padded_bases of ONE record as long as the file's text
+ * always suffices.  Per file (host arrays of n_files entries, each nullable):
+ * length (sequence bytes), padded span, record count, valid k-mer positions
+ * for the context's k, and status: 0 packed; 1 the file holds a record line
+ * starting with '+' (FASTQ) and needs the host reader, nothing was packed;
+ * 2 the region is too small, nothing was written.  Nothing outside a file's
+ * region is ever written.  Runs on `stream`; blocking. */
+int drephip_fasta_pack_device(drephip_ctx *ctx, const uint8_t *d_text, const uint64_t *h_text_off,
+                              uint32_t n_files, const uint64_t *h_base_off, const uint64_t *h_cap_bases,
+                              uint32_t *d_codes, uint32_t *d_valid, uint64_t *length_out, uint64_t *padded_out,
+                              uint32_t *n_records_out, uint64_t *n_kmers_out, uint8_t *status_out, void *stream);
+
+/* Who parses and packs the files of drephip_sketch_files.  HOST (the default):
+ * worker threads, as described above.  DEVICE: the workers only read each
+ * plain file's bytes into pinned memory; the text is copied to the device,
+ * packed there (drephip_fasta_pack_device) and sketched in place.  gzip files
+ * and files with FASTQ records still take the host reader, file by file.  The
+ * results are identical.  A new context takes its path from the environment
+ * variable DREPHIP_INGEST=host|device when it is set.  On the DEVICE path
+ * drephip_last_ingest_stats / _phases keep their meaning: read_thread_s is the
+ * raw read (plus the host reader's share for gzip and FASTQ files),
+ * pack_thread_s counts only the files the host packed, and gpu_s includes the
+ * text copy and the pack kernels. */
+#define DREPHIP_INGEST_HOST   0
+#define DREPHIP_INGEST_DEVICE 1
+int drephip_set_ingest_path(drephip_ctx *ctx, int path);
+int drephip_get_ingest_path(drephip_ctx *ctx, int *path);
+
+/* The last drephip_sketch_files call: files packed on the device, files that
+ * took the host reader, and bytes of text copied to the device (0, n, 0 after
+ * a HOST-path call). */
+int drephip_last_ingest_paths(drephip_ctx *ctx, uint32_t *device_files, uint32_t *host_files,
+                              uint64_t *text_bytes);
+
 /* Device-resident sketch: packed genome set already in HBM (see layout).
  * h_base_off/h_padded/h_nkmers are host arrays of n_genomes entries
  * (h_nkmers: valid k-mer positions, used only to seed the candidate
