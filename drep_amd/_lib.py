@@ -94,6 +94,16 @@ SIGNATURES = {
                                                         vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]),
     "drephip_allpairs_sparse": (C.c_int, [vp, u64p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64,
                                           C.POINTER(C.c_uint64)]),
+    "drephip_dist_rect_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           vp, vp, vp]),
+    "drephip_dist_rect_merge_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 vp, vp, vp]),
+    "drephip_dist_rect": (C.c_int, [vp, u64p, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                    vp, vp]),
+    "drephip_dist_rect_sparse_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  vp, C.c_uint64, C.POINTER(C.c_uint64), vp]),
+    "drephip_dist_rect_sparse": (C.c_int, [vp, u64p, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "drephip_last_sparse_stats": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint64)]),
     "drephip_distance_lut": (C.c_int, [C.c_int, C.c_uint32, f64p]),
@@ -401,6 +411,23 @@ def linkage_sparse(n: int, i: np.ndarray, j: np.ndarray, v: np.ndarray, method: 
                                            v if len(v) else np.zeros(1), LINK_METHODS[method], Z.reshape(-1)),
               "drephip_linkage_sparse")
     return Z
+
+
+def rect_arrays(qhashes, qnhash, rhashes, rnhash, s: int):
+    """The two sketch matrices of a query-against-reference call, contiguous:
+    hashes uint64 [rows, s], nhash uint32 [rows].  ValueError for any other
+    dtype or shape (no conversion: a float or signed matrix is a caller's
+    mistake, not a sketch); needs no library and no GPU."""
+    out = []
+    for side, h, n in (("query", qhashes, qnhash), ("reference", rhashes, rnhash)):
+        h, n = np.asarray(h), np.asarray(n)
+        if h.dtype != np.uint64 or n.dtype != np.uint32:
+            raise ValueError("%s hashes / nhash must be uint64 / uint32, got %s / %s" % (side, h.dtype, n.dtype))
+        if n.ndim != 1 or h.ndim != 2 or h.shape != (len(n), int(s)):
+            raise ValueError("%s hashes must be [rows, s] = [%d, %d] with nhash [rows], got %s and %s"
+                             % (side, len(n) if n.ndim == 1 else -1, int(s), h.shape, n.shape))
+        out += [np.ascontiguousarray(h), np.ascontiguousarray(n)]
+    return tuple(out)
 
 
 class Context:
@@ -783,6 +810,118 @@ class Context:
         if rc != self.ERR_NOMEM:
             check(rc, "drephip_allpairs_sparse_device_marked")
         return rc, n.value
+
+    # -- query against reference (include/drephip.h: drephip_dist_rect ...)
+    def _rect_range(self, Q: int, q0: int, q1: Optional[int]) -> Tuple[int, int]:
+        q0 = int(q0)
+        q1 = Q if q1 is None else min(int(q1), Q)
+        if q0 < 0 or q1 < 0:
+            raise ValueError("q0 and q1 must not be negative")
+        return q0, q1
+
+    def dist_rect(self, qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray,
+                  q0: int = 0, q1: Optional[int] = None, common_out: Optional[np.ndarray] = None,
+                  denom_out: Optional[np.ndarray] = None):
+        """`mash dist <reference> <query>` as counts: (common, denom), uint16
+        [q1 - q0, N], for query rows [q0, q1) against every reference row
+        (drephip_dist_rect).  common_out / denom_out: contiguous uint16 buffers
+        of at least (q1 - q0) * N entries to write into instead."""
+        qhashes, qnhash, rhashes, rnhash = rect_arrays(qhashes, qnhash, rhashes, rnhash, self.s)
+        Q, N = len(qnhash), len(rnhash)
+        q0, q1 = self._rect_range(Q, q0, q1)
+        rows = max(0, q1 - q0)
+        for arr in (common_out, denom_out):
+            if arr is not None and (arr.dtype != np.uint16 or not arr.flags.c_contiguous or arr.size < rows * N):
+                raise ValueError("output buffers must be contiguous uint16 of at least %d entries" % (rows * N))
+        common = common_out if common_out is not None else np.zeros((rows, N), dtype=np.uint16)
+        denom = denom_out if denom_out is not None else np.zeros((rows, N), dtype=np.uint16)
+        check(lib().drephip_dist_rect(self._h, qhashes.reshape(-1), qnhash, Q, rhashes.reshape(-1), rnhash, N, q0, q1,
+                                      common.ctypes.data, denom.ctypes.data), "drephip_dist_rect")
+        return common, denom
+
+    def dist_rect_device(self, d_qhashes: int, d_qnhash: int, Q: int, d_rhashes: int, d_rnhash: int, N: int,
+                         q0: int, q1: int, d_common: int, d_denom: Optional[int] = None,
+                         stream: Optional[int] = None, merge: bool = False) -> None:
+        fn = lib().drephip_dist_rect_merge_device if merge else lib().drephip_dist_rect_device
+        check(fn(self._h, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1, d_common, d_denom, stream),
+              "drephip_dist_rect_merge_device" if merge else "drephip_dist_rect_device")
+
+    def dist_rect_merge(self, qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray,
+                        q0: int = 0, q1: Optional[int] = None):
+        """dist_rect by the literal merge kernel (drephip_dist_rect_merge_device;
+        the cross-check): the matrices are staged with torch on this context's
+        device."""
+        import torch
+        qhashes, qnhash, rhashes, rnhash = rect_arrays(qhashes, qnhash, rhashes, rnhash, self.s)
+        Q, N = len(qnhash), len(rnhash)
+        q0, q1 = self._rect_range(Q, q0, q1)
+        rows = max(0, q1 - q0)
+        if rows == 0 or N == 0:
+            return np.zeros((rows, N), dtype=np.uint16), np.zeros((rows, N), dtype=np.uint16)
+        dev = torch.device("cuda", self.device)
+
+        def up(a, view):
+            return torch.tensor(a.view(view), device=dev)      # (a copy: the input may be read-only)
+        with torch.cuda.device(dev):
+            d_qh, d_qn = up(qhashes, np.int64), up(qnhash, np.int32)
+            d_rh, d_rn = up(rhashes, np.int64), up(rnhash, np.int32)
+            d_c = torch.zeros((rows, N), dtype=torch.int16, device=dev)
+            d_d = torch.zeros((rows, N), dtype=torch.int16, device=dev)
+            torch.cuda.synchronize(dev)
+            self.dist_rect_device(d_qh.data_ptr(), d_qn.data_ptr(), Q, d_rh.data_ptr(), d_rn.data_ptr(), N, q0, q1,
+                                  d_c.data_ptr(), d_d.data_ptr(), merge=True)
+            return d_c.cpu().numpy().view(np.uint16), d_d.cpu().numpy().view(np.uint16)
+
+    def dist_rect_sparse_raw(self, qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray,
+                             q0: int, q1: Optional[int], pairs: Optional[np.ndarray]) -> Tuple[int, int]:
+        """One drephip_dist_rect_sparse call into `pairs` (uint32 [cap, 4],
+        contiguous; None: count only): (return code, records the rows hold).
+        Raises on every error but DREPHIP_ERR_NOMEM (the buffer is too small)."""
+        qhashes, qnhash, rhashes, rnhash = rect_arrays(qhashes, qnhash, rhashes, rnhash, self.s)
+        Q, N = len(qnhash), len(rnhash)
+        q0, q1 = self._rect_range(Q, q0, q1)
+        cap = 0
+        if pairs is not None:
+            if pairs.dtype != np.uint32 or not pairs.flags.c_contiguous or pairs.ndim != 2 or pairs.shape[1] != 4:
+                raise ValueError("pairs must be a contiguous uint32 [cap, 4] array")
+            cap = len(pairs)
+        n = C.c_uint64(0)
+        rc = lib().drephip_dist_rect_sparse(self._h, qhashes.reshape(-1), qnhash, Q, rhashes.reshape(-1), rnhash, N,
+                                            q0, q1, pairs.ctypes.data if cap else None, cap, C.byref(n))
+        if rc != self.ERR_NOMEM:
+            check(rc, "drephip_dist_rect_sparse")
+        return rc, n.value
+
+    def dist_rect_sparse_device(self, d_qhashes: int, d_qnhash: int, Q: int, d_rhashes: int, d_rnhash: int, N: int,
+                                q0: int, q1: int, d_pairs: Optional[int], cap: int,
+                                stream: Optional[int] = None) -> Tuple[int, int]:
+        """drephip_dist_rect_sparse_device: (return code, records the rows hold);
+        raises on every error but DREPHIP_ERR_NOMEM."""
+        n = C.c_uint64(0)
+        rc = lib().drephip_dist_rect_sparse_device(self._h, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1,
+                                                   d_pairs, cap, C.byref(n), stream)
+        if rc != self.ERR_NOMEM:
+            check(rc, "drephip_dist_rect_sparse_device")
+        return rc, n.value
+
+    def dist_rect_sparse(self, qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray,
+                         q0: int = 0, q1: Optional[int] = None, cap: Optional[int] = None):
+        """The (query, reference) pairs of query rows [q0, q1) that share a hash,
+        as (q, r, common, denom) -- uint32, uint32, uint16, uint16 -- sorted by
+        (q, r); every pair not listed has common 0.  `cap`: records to make room
+        for at first (default 8 per query + 4096); when the rows hold more, the
+        call is repeated once with the size the library reports."""
+        cap = int(cap) if cap is not None else 8 * len(qnhash) + 4096
+        buf = np.empty((max(cap, 1), 4), dtype=np.uint32)
+        rc, n = self.dist_rect_sparse_raw(qhashes, qnhash, rhashes, rnhash, q0, q1, buf[:cap] if cap else None)
+        if rc == self.ERR_NOMEM:
+            buf = np.empty((n, 4), dtype=np.uint32)
+            rc, n = self.dist_rect_sparse_raw(qhashes, qnhash, rhashes, rnhash, q0, q1, buf)
+            check(rc, "drephip_dist_rect_sparse")
+        rec = buf[:n]
+        rec = rec[np.lexsort((rec[:, 1], rec[:, 0]))]
+        return (np.ascontiguousarray(rec[:, 0]), np.ascontiguousarray(rec[:, 1]),
+                rec[:, 2].astype(np.uint16), rec[:, 3].astype(np.uint16))
 
     def sparse_stats(self) -> dict:
         """{blocks, direct, fallback, scratch_bytes} of the last sparse all-pairs call."""

@@ -486,8 +486,15 @@ __device__ __forceinline__ uint64_t ld_chunk_at(__amdgpu_buffer_rsrc_t rs, uint3
 // denominator and row packed -- s <= 2048 on this path); when fewer than R
 // lanes are free, and after the item's last column, the wave reserves its
 // staged records' slots with one atomic add and stores them (sparse.h).
+//
+// RECT (drephip_dist_rect_device): the columns are the sketches of a second
+// matrix -- the caller passes that matrix as hashes / nhash / N, the row side
+// reaches this function only through the LDS image and the per-row scalars --
+// so there is no diagonal: every active row meets every column, its own
+// sketch included.  The output is the row-major rectangle: pair (i, c) at
+// i * N + c - seg0 (seg0 = the call's first row x N), each next row + N.
 template <int R, int NCH, bool FAST, int KB, bool MASKED, bool LIST = false, bool HITQ = false, bool HITV = false,
-          bool COLL = false, bool SPARSE = false>
+          bool COLL = false, bool SPARSE = false, bool RECT = false>
 __device__ __forceinline__ void ap_columns(const uint64_t *__restrict__ hashes, const uint32_t *__restrict__ nhash,
                                            const uint32_t *T, const uint32_t *V, uint32_t H, uint32_t hm, uint32_t s,
                                            uint32_t N, uint32_t i0, uint32_t nrows, uint32_t cend, uint32_t c_first,
@@ -558,7 +565,7 @@ __device__ __forceinline__ void ap_columns(const uint64_t *__restrict__ hashes, 
         act_full |= (uint32_t)act << r;
         if (act) amax_full = alast[r] > amax_full ? alast[r] : amax_full;
     }
-    const uint64_t obase = cond_index(i0, 0, N) - seg0;            // + c: row i0's pair (i0, c)
+    const uint64_t obase = (RECT ? (uint64_t)i0 * N : cond_index(i0, 0, N)) - seg0;   // + c: row i0's pair (i0, c)
     for (uint32_t cnext = 0; kc < cend; kc += c_step, c = cnext) {
         const __amdgpu_buffer_rsrc_t rc = column_rsrc(hashes + (uint64_t)c * s, s);
 #pragma unroll
@@ -579,14 +586,16 @@ __device__ __forceinline__ void ap_columns(const uint64_t *__restrict__ hashes, 
 #pragma unroll
         for (int r = 0; r < R; r++) { cnt[r] = 0; mrun[r] = 0; nb[r] = -(int32_t)s; }
         auto mrun_of = [&](int r) -> uint32_t { return HITV ? (uint32_t)(-nb[r] - (int32_t)s) : mrun[r]; };
-        if (c < i0 + R) {                                             // the diagonal tile: rows right of c drop out
-            actmask = 0;
-            amax = 0;
+        if constexpr (!RECT) {
+            if (c < i0 + R) {                                         // the diagonal tile: rows right of c drop out
+                actmask = 0;
+                amax = 0;
 #pragma unroll
-            for (int r = 0; r < R; r++) {
-                const bool act = ((act_full >> r) & 1u) && i0 + r < c;
-                actmask |= (uint32_t)act << r;
-                if (act) amax = alast[r] > amax ? alast[r] : amax;
+                for (int r = 0; r < R; r++) {
+                    const bool act = ((act_full >> r) & 1u) && i0 + r < c;
+                    actmask |= (uint32_t)act << r;
+                    if (act) amax = alast[r] > amax ? alast[r] : amax;
+                }
             }
         }
         if (!actmask) continue;                                       // column at or left of the tile's rows
@@ -758,7 +767,7 @@ __device__ __forceinline__ void ap_columns(const uint64_t *__restrict__ hashes, 
             uint64_t o = obase + c;
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                if (r > 0) o += N - (i0 + r - 1) - 2;                   // cond_index(i0 + r, c) - seg0
+                if (r > 0) o += RECT ? N : N - (i0 + r - 1) - 2;        // cond_index(i0 + r, c) - seg0
                 if (!((actmask >> r) & 1u)) continue;
                 common[o] = (uint16_t)cnt[r];
                 if (denom) {
@@ -784,15 +793,31 @@ __host__ __device__ constexpr size_t q_lds_bytes(uint32_t R, uint32_t TS, uint32
 // (LDS <= 80 KiB, <= 64 VGPRs).
 // LIST: items are {i0, list offset, count, 0} over the screened column list
 // (screen.hip); otherwise {i0, c0, cend, 0} over the column range.
-// SPARSE (with LIST): records of the non-zero pairs instead (ap_columns).
-template <int R, int NCH, int MINW, bool LIST = false, bool SPARSE = false>
+// SPARSE (with LIST or RECT): records of the non-zero pairs instead (ap_columns).
+// RECT (drephip_dist_rect_device): the rows [row0, row1) are queries (hashes,
+// nhash: the query matrix, whose images k_build_q32 built) and the columns the
+// rc.n sketches of the reference matrix rc; items are {i0, c0, cend, 0} over
+// every (row tile, column tile) pair, the output the (row1 - row0) x rc.n
+// rectangle, row-major.  No screen: neither LIST nor chunk masks.
+struct RectCols {
+    const uint64_t *hashes = nullptr;
+    const uint32_t *nhash = nullptr;
+    uint32_t n = 0;
+};
+template <int R, int NCH, int MINW, bool LIST = false, bool SPARSE = false, bool RECT = false>
 __global__ __launch_bounds__(kApWG, MINW) void k_allpairs_q(
     const uint64_t *__restrict__ hashes, const uint32_t *__restrict__ nhash,
     const uint32_t *__restrict__ blk, uint32_t stride, const uint8_t *__restrict__ fam, uint32_t s, uint32_t N,
     uint32_t row0, uint32_t row1, uint32_t B, const uint4 *__restrict__ items,
     uint16_t *__restrict__ common, uint16_t *__restrict__ denom, uint64_t seg0, const uint32_t *__restrict__ clist,
-    int hitq, const uint32_t *__restrict__ cmask, SparseOut sp) {
-    static_assert(LIST || !SPARSE, "the SPARSE flavour runs on the screened lists");
+    int hitq, const uint32_t *__restrict__ cmask, SparseOut sp, RectCols rc = RectCols{}) {
+    static_assert(LIST || RECT || !SPARSE, "the SPARSE flavour runs on the screened lists or the rectangle");
+    static_assert(!(RECT && LIST), "the rectangle has no screen");
+    // the column side: the matrix itself, or (RECT) the reference matrix
+    const uint64_t *__restrict__ chashes = RECT ? rc.hashes : hashes;
+    const uint32_t *__restrict__ cnhash = RECT ? rc.nhash : nhash;
+    const uint32_t Nc = RECT ? rc.n : N;
+    if constexpr (RECT) seg0 = (uint64_t)row0 * Nc;     // pair (i, c) at i * Nc + c - seg0
     constexpr int WG = kApWG;
     extern __shared__ __align__(16) uint32_t lds[];    // 16-B aligned: slot words are read with ds_read_b128
     const uint32_t H = 1u << B, hm = H - 1, TS = 2 * H;
@@ -803,7 +828,7 @@ __global__ __launch_bounds__(kApWG, MINW) void k_allpairs_q(
     if (i0 == 0xFFFFFFFFu) return;                      // idle padding item (make_items)
     const uint32_t nrows = min((uint32_t)R, row1 - i0);
     // LIST: c0 = the item's list offset, cend = its column count
-    const uint32_t cend = LIST ? items[blockIdx.x].z : min(items[blockIdx.x].z, N);
+    const uint32_t cend = LIST ? items[blockIdx.x].z : min(items[blockIdx.x].z, Nc);
     const uint32_t *ilist = LIST ? clist + c0 : nullptr;
     const uint32_t cfirst = LIST ? 0 : c0;
     const uint32_t tid = threadIdx.x, wave = tid >> 6;
@@ -871,28 +896,28 @@ __global__ __launch_bounds__(kApWG, MINW) void k_allpairs_q(
     // The kernel declares no static LDS (.group_segment_fixed_size 0, checked
     // by tests/test_host.py), so `lds` is LDS address 0 (read_slots).
     constexpr int KB = NCH == 16 ? 11 : 0;
-    if (fast && !zero_key && hitq && !LIST && cmask)
+    // (the column side chashes / cnhash / Nc is all ap_columns reads of a matrix)
+    if (fast && !zero_key && hitq && !LIST && !RECT && cmask)
         // the dense path after the screen's verdict: chunk masks (probe_rows_v)
-        ap_columns<R, NCH, true, KB, false, LIST, true, true, !LIST>(hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend,
-                                                                    cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1,
-                                                                    thr2, ~failmask, any_partial_row, common, denom, seg0,
-                                                                    cmask);
+        ap_columns<R, NCH, true, KB, false, LIST, true, true, !LIST && !RECT>(
+            chashes, cnhash, T, V, H, hm, s, Nc, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1,
+            thr2, ~failmask, any_partial_row, common, denom, seg0, cmask);
     else if (fast && !zero_key && hitq)
-        ap_columns<R, NCH, true, KB, false, LIST, true, true, false, SPARSE>(
-            hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1, thr2,
-            ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
+        ap_columns<R, NCH, true, KB, false, LIST, true, true, false, SPARSE, RECT>(
+            chashes, cnhash, T, V, H, hm, s, Nc, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1,
+            thr2, ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
     else if (fast && !zero_key)
-        ap_columns<R, NCH, true, KB, false, LIST, false, false, false, SPARSE>(
-            hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1, thr2,
-            ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
+        ap_columns<R, NCH, true, KB, false, LIST, false, false, false, SPARSE, RECT>(
+            chashes, cnhash, T, V, H, hm, s, Nc, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1,
+            thr2, ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
     else if (fast)
-        ap_columns<R, NCH, true, KB, true, LIST, false, false, false, SPARSE>(
-            hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1, thr2,
-            ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
+        ap_columns<R, NCH, true, KB, true, LIST, false, false, false, SPARSE, RECT>(
+            chashes, cnhash, T, V, H, hm, s, Nc, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1,
+            thr2, ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
     else
-        ap_columns<R, NCH, false, KB, true, LIST, false, false, false, SPARSE>(
-            hashes, nhash, T, V, H, hm, s, N, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1, thr2,
-            ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
+        ap_columns<R, NCH, false, KB, true, LIST, false, false, false, SPARSE, RECT>(
+            chashes, cnhash, T, V, H, hm, s, Nc, i0, nrows, cend, cfirst + wave, WG / 64, ilist, nA, o1, o2, alast, thr1,
+            thr2, ~failmask, any_partial_row, common, denom, seg0, nullptr, sp);
     if (failmask) {
         // a row whose table could not be built (three of its keys share a low
         // word under every field family; never observed on real sketches):
@@ -900,13 +925,14 @@ __global__ __launch_bounds__(kApWG, MINW) void k_allpairs_q(
         const uint32_t ncol = cend - cfirst;
         for (uint32_t t = tid; t < (uint32_t)R * ncol; t += WG) {
             const uint32_t r = t / ncol, c = LIST ? ilist[t % ncol] : c0 + t % ncol, i = i0 + r;
-            if (!((failmask >> r) & 1u) || c <= i) continue;
+            if (!((failmask >> r) & 1u)) continue;
+            if constexpr (!RECT) { if (c <= i) continue; }
             uint32_t cm, dd;
-            merge_pair(hashes + (uint64_t)i * s, nhash[i], hashes + (uint64_t)c * s, nhash[c], s, cm, dd);
+            merge_pair(hashes + (uint64_t)i * s, nhash[i], chashes + (uint64_t)c * s, cnhash[c], s, cm, dd);
             if constexpr (SPARSE) {
                 if (cm) sparse_append(sp, i, c, cm, dd);
             } else {
-                const uint64_t o = cond_index(i, c, N) - seg0;
+                const uint64_t o = (RECT ? (uint64_t)i * Nc + c : cond_index(i, c, N)) - seg0;
                 common[o] = (uint16_t)cm;
                 if (denom) denom[o] = (uint16_t)dd;
             }
@@ -1917,6 +1943,286 @@ int allpairs_sparse_list_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const 
 #undef DREPHIP_QS
 #undef DREPHIP_QS1
     return rc;
+}
+
+// ------------------------------------------------- query against reference
+// `mash dist <reference.msh> <query.msh>`: rows [q0, q1) of the Q x N
+// rectangle, row-major.
+//
+// The literal Mash merge, one lane per (q, r) pair of `npairs` cells from cell
+// `first` of the call's rectangle (cell t = (q - q0) * N + r): the cross-check
+// of the RECT kernel, and the route for s > 2048 and DREPHIP_AP_MERGE.
+__global__ __launch_bounds__(256) void k_rect_merge(const uint64_t *__restrict__ qhashes,
+                                                    const uint32_t *__restrict__ qnhash,
+                                                    const uint64_t *__restrict__ rhashes,
+                                                    const uint32_t *__restrict__ rnhash, uint32_t s, uint32_t N,
+                                                    uint32_t q0, uint64_t first, uint64_t npairs,
+                                                    uint16_t *__restrict__ common, uint16_t *__restrict__ denom) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= npairs) return;
+    const uint64_t cell = first + t;
+    const uint32_t q = q0 + (uint32_t)(cell / N), r = (uint32_t)(cell % N);
+    uint32_t c, d;
+    merge_pair(qhashes + (uint64_t)q * s, qnhash[q], rhashes + (uint64_t)r * s, rnhash[r], s, c, d);
+    common[cell] = (uint16_t)c;
+    if (denom) denom[cell] = (uint16_t)d;
+}
+
+// The non-zero cells among `ncells` cells from cell `first` of a block's
+// scratch rectangle (rows from q0) as records {q, r, common, denom}
+__global__ __launch_bounds__(256) void k_rect_compact(const uint16_t *__restrict__ common,
+                                                      const uint16_t *__restrict__ denom, uint32_t N, uint32_t q0,
+                                                      uint64_t first, uint64_t ncells, SparseOut sp) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ncells) return;
+    const uint64_t cell = first + t;
+    const uint32_t c = common[cell];
+    if (c) sparse_append(sp, q0 + (uint32_t)(cell / N), (uint32_t)(cell % N), c, denom[cell]);
+}
+
+static int launch_rect_merge(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, const uint64_t *d_rh,
+                             const uint32_t *d_rn, uint32_t N, uint32_t q0, uint64_t cells, uint16_t *d_common,
+                             uint16_t *d_denom, hipStream_t st) {
+    const uint64_t per = max_blocks(256) * 256;      // pairs per dispatch
+    timing_mark(ctx, 2, st, true);
+    for (uint64_t p0 = 0; p0 < cells; p0 += per) {
+        const uint64_t np = std::min(per, cells - p0);
+        hipLaunchKernelGGL(k_rect_merge, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, st, d_qh, d_qn, d_rh, d_rn,
+                           ctx->s, N, q0, p0, np, d_common, d_denom);
+    }
+    timing_mark(ctx, 2, st, false);
+    HIPC(hipGetLastError());
+    return DREPHIP_OK;
+}
+
+// Work items of the rectangle: every (row tile, column tile) pair, in the
+// order plan_items gives the triangle's -- the groups (runs of one column
+// tile's row tiles) dealt to the 8 XCDs, largest first, so the workgroups of
+// one XCD stream the same ~C reference sketches.
+static ItemPlan plan_rect_items(uint32_t q0, uint32_t q1, uint32_t Nc, uint32_t R, uint32_t C) {
+    const uint32_t nct = (Nc + C - 1) / C;
+    const uint64_t nrt = ((uint64_t)(q1 - q0) + R - 1) / R;
+    const uint64_t total = nrt * nct;
+    const uint64_t gmax = std::max<uint64_t>(1, total / (kXcds * 16));
+    std::vector<std::vector<ItemGroup>> lists(kXcds);
+    uint64_t len[kXcds] = {};
+    // every tile has nrt items: whole runs of gmax first, then the remainders
+    // (the largest-first order of plan_items)
+    for (int pass = 0; pass < 2; pass++)
+        for (uint32_t ct = 0; ct < nct; ct++)
+            for (uint64_t i = 0; i < nrt; i += gmax) {
+                const uint64_t size = std::min(gmax, nrt - i);
+                if ((size == gmax) != (pass == 0)) continue;
+                uint32_t best = 0;
+                for (uint32_t x = 1; x < kXcds; x++) if (len[x] < len[best]) best = x;
+                lists[best].push_back({(uint32_t)(q0 + i * R), ct * C, (uint32_t)len[best], (uint32_t)size});
+                len[best] += size;
+            }
+    ItemPlan p;
+    uint64_t lmax = 0;
+    for (uint32_t x = 0; x < kXcds; x++) {
+        p.xs.v[x] = (uint32_t)p.groups.size();
+        p.groups.insert(p.groups.end(), lists[x].begin(), lists[x].end());
+        lmax = std::max(lmax, len[x]);
+    }
+    p.xs.v[kXcds] = (uint32_t)p.groups.size();
+    p.slots = lmax * kXcds;
+    return p;
+}
+
+template <int R, int NCH, int MINW, bool SPARSE>
+static int launch_rect_q(drephip_ctx *ctx, uint32_t nitems, size_t lds, hipStream_t st, const uint64_t *qh,
+                         const uint32_t *qn, const uint32_t *blk, uint32_t stride, const uint8_t *fam, uint32_t Q,
+                         uint32_t q0, uint32_t q1, uint32_t B, const uint4 *items, uint16_t *cm, uint16_t *dn,
+                         const RectCols &rc, const SparseOut &sp) {
+    HIPC(hipFuncSetAttribute((const void *)k_allpairs_q<R, NCH, MINW, false, SPARSE, true>,
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const char *he = getenv("DREPHIP_AP_HIT");         // as launch_q
+    const int hitq = he ? atoi(he) : 1;
+    timing_mark(ctx, 2, st, true);
+    for (uint32_t i0 = 0; i0 < nitems; i0 += (uint32_t)max_blocks(kApWG))
+        hipLaunchKernelGGL((k_allpairs_q<R, NCH, MINW, false, SPARSE, true>),
+                           dim3(std::min<uint32_t>(nitems - i0, (uint32_t)max_blocks(kApWG))), dim3(kApWG), lds, st, qh,
+                           qn, blk, stride, fam, ctx->s, Q, q0, q1, B, items + i0, cm, dn, 0ull, nullptr, hitq, nullptr,
+                           sp, rc);
+    timing_mark(ctx, 2, st, false);
+    HIPC(hipGetLastError());
+    return DREPHIP_OK;
+}
+
+// Rows [q0, q1) through the RECT flavour of the whole-row kernel: the query
+// rows' images by k_build_q32, the item plan, the launch.  sp == null: the
+// rectangle into d_common / d_denom; else records into *sp.  Queued on st.
+static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
+                      const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint32_t R, uint16_t *d_common,
+                      uint16_t *d_denom, const SparseOut *sp, std::vector<ItemGroup> &groups, hipStream_t st) {
+    const uint32_t s = ctx->s;
+    uint32_t B = 4;
+    while ((1u << B) < 2 * s) B++;
+    const uint32_t TS = 2u << B;
+    const uint32_t nrows = q1 - q0;
+    const uint32_t ngroups = (nrows + R - 1) / R;
+    const uint32_t stride = (uint32_t)((q_lds_bytes(R, TS, s) / 4 + 3) & ~3ull);   // words, 16-B multiple
+    uint32_t *d_blk;
+    uint8_t *d_fam;
+    uint4 *d_items;
+    int rc;
+    if ((rc = scratch(ctx, "ap_blk", (uint64_t)ngroups * stride * 4, (void **)&d_blk))) return rc;
+    if ((rc = scratch(ctx, "ap_fam", ((uint64_t)ngroups * R + 7) & ~7ull, (void **)&d_fam))) return rc;
+    const size_t blds = (size_t)TS * 4;
+    HIPC(hipFuncSetAttribute((const void *)k_build_q32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds));
+    timing_mark(ctx, 3, st, true);
+    hipLaunchKernelGGL(k_build_q32, dim3(ngroups * R), dim3(1024), blds, st, d_qh, d_qn, s, q0, q1, B, R, d_blk, stride,
+                       d_fam);
+    timing_mark(ctx, 3, st, false);
+    HIPC(hipGetLastError());
+    // column tile: the rule of the triangle's plan -- the widest (<= kApCols)
+    // that still gives every workgroup slot of the chip about four items
+    uint32_t C = kApCols;
+    auto nitems_for = [&](uint32_t c) { return (uint64_t)ngroups * ((N + c - 1) / c); };
+    while (C > kApMinCols && nitems_for(C) < 4ull * kApSlots) C /= 2;
+    if (nitems_for(C) + kXcds * 16ull >= (1ull << 32)) {
+        set_error("the rectangle's item list exceeds 2^32 entries: call it in row ranges");
+        return DREPHIP_ERR_UNSUPPORTED;
+    }
+    // the plan is not cached: its key (Q, q0, q1, N, R, C) is not the
+    // triangle's, and planning is a few thousand groups on the host
+    uint64_t ni64;
+    if ((rc = expand_items<true>(ctx, plan_rect_items(q0, q1, N, R, C), groups, "rect_items", R, C, st,
+                                 (void **)&d_items, &ni64)))
+        return rc;
+    const uint32_t ni = (uint32_t)ni64;
+    const size_t lds = (size_t)stride * 4;
+    const uint32_t nch = (s + 63) / 64;
+    const bool two = lds <= 80 * 1024;              // two workgroups per CU when the LDS allows
+    const RectCols cols{d_rh, d_rn, N};
+    const SparseOut out = sp ? *sp : SparseOut{};
+#define DREPHIP_QR1(RR, NC, MW, SP) launch_rect_q<RR, NC, MW, SP>(ctx, ni, lds, st, d_qh, d_qn, d_blk, stride, d_fam, Q, q0, q1, B, \
+                                                                  d_items, d_common, d_denom, cols, out)
+#define DREPHIP_QR(RR, NC) (two ? (sp ? DREPHIP_QR1(RR, NC, 8, true) : DREPHIP_QR1(RR, NC, 8, false)) \
+                                : (sp ? DREPHIP_QR1(RR, NC, 4, true) : DREPHIP_QR1(RR, NC, 4, false)))
+    if (nch <= 8) {
+        switch (R) {
+            case 8: rc = DREPHIP_QR(8, 8); break;
+            case 4: rc = DREPHIP_QR(4, 8); break;
+            case 2: rc = DREPHIP_QR(2, 8); break;
+            default: rc = DREPHIP_QR(1, 8); break;
+        }
+    } else if (nch <= 16) {
+        switch (R) {
+            case 8: rc = DREPHIP_QR(8, 16); break;
+            case 4: rc = DREPHIP_QR(4, 16); break;
+            case 2: rc = DREPHIP_QR(2, 16); break;
+            default: rc = DREPHIP_QR(1, 16); break;
+        }
+    } else {
+        switch (R) {
+            case 4: rc = DREPHIP_QR(4, 32); break;
+            case 2: rc = DREPHIP_QR(2, 32); break;
+            default: rc = DREPHIP_QR(1, 32); break;
+        }
+    }
+#undef DREPHIP_QR
+#undef DREPHIP_QR1
+    return rc;
+}
+
+// the rectangle's kernel for this context: the whole-row table kernel when its
+// tables fit (s <= 2048), k_rect_merge otherwise and on request; no band kernel
+static int rect_path(drephip_ctx *ctx, bool force_merge, uint32_t *R, int *path) {
+    *R = 1;
+    *path = DREPHIP_AP_MERGE;
+    if (force_merge || ctx->ap_path == DREPHIP_AP_MERGE) return DREPHIP_OK;
+    if (ctx->ap_path == DREPHIP_AP_BAND) {
+        set_error("the query-against-reference rectangle has no band kernel: DREPHIP_AP_AUTO, _TABLE or _MERGE");
+        return DREPHIP_ERR_UNSUPPORTED;
+    }
+    int p;
+    int rc = allpairs_geometry(ctx, R, &p);         // (DREPHIP_AP_TABLE with s > 2048: its error)
+    if (rc) return rc;
+    if (p == DREPHIP_AP_TABLE) *path = DREPHIP_AP_TABLE;
+    else *R = 1;                                    // AUTO past the tables: the merge kernel
+    return DREPHIP_OK;
+}
+
+int rect_device_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
+                     const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint16_t *d_common,
+                     uint16_t *d_denom, hipStream_t st, bool force_merge) {
+    if (ctx->apend.active) {
+        int rc = allpairs_wait_impl(ctx);
+        if (rc) return rc;
+    }
+    if (q1 > Q) q1 = Q;
+    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
+    uint32_t R;
+    int path, rc;
+    if ((rc = rect_path(ctx, force_merge, &R, &path))) return rc;
+    ctx->last_screen = ScreenResult{};
+    std::vector<ItemGroup> groups;                   // lives until the stream sync below
+    if (path == DREPHIP_AP_MERGE)
+        rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
+    else
+        rc = rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, R, d_common, d_denom, nullptr, groups, st);
+    if (rc) return rc;
+    HIPC(hipStreamSynchronize(st));
+    return DREPHIP_OK;
+}
+
+constexpr uint64_t kRectBlockPairs = 1ull << 28;    // cells per scratch rectangle of the merge route's records
+
+int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
+                     const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint4 *d_pairs, uint64_t cap,
+                     uint64_t *n_pairs, hipStream_t st) {
+    *n_pairs = 0;
+    if (ctx->apend.active) {
+        int rc = allpairs_wait_impl(ctx);
+        if (rc) return rc;
+    }
+    if (q1 > Q) q1 = Q;
+    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
+    uint32_t R;
+    int path, rc;
+    if ((rc = rect_path(ctx, false, &R, &path))) return rc;
+    ctx->last_screen = ScreenResult{};
+    unsigned long long *d_count;
+    uint64_t *h_tot;
+    if ((rc = scratch(ctx, "sp_count", 8, (void **)&d_count))) return rc;
+    if ((rc = pinned_host(ctx, "sp_tot", 64, (void **)&h_tot))) return rc;
+    HIPC(hipMemsetAsync(d_count, 0, 8, st));
+    const SparseOut out{d_pairs, d_count, cap};
+    std::vector<ItemGroup> groups;                   // lives until the stream sync below
+    if (path == DREPHIP_AP_TABLE) {
+        if ((rc = rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, R, nullptr, nullptr, &out, groups, st))) return rc;
+    } else {
+        // query-row blocks of at most kRectBlockPairs cells (at least one row)
+        const uint32_t rows = (uint32_t)std::max<uint64_t>(1, kRectBlockPairs / N);
+        const uint64_t bcells = (uint64_t)std::min<uint32_t>(rows, q1 - q0) * N;
+        uint16_t *d_c, *d_d;
+        if ((rc = scratch(ctx, "rect_blk_common", bcells * 2, (void **)&d_c))) return rc;
+        if ((rc = scratch(ctx, "rect_blk_denom", bcells * 2, (void **)&d_d))) return rc;
+        for (uint32_t b0 = q0; b0 < q1;) {
+            const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
+            const uint64_t cells = (uint64_t)(b1 - b0) * N;
+            if ((rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, cells, d_c, d_d, st))) return rc;
+            const uint64_t per = max_blocks(256) * 256;
+            for (uint64_t p0 = 0; p0 < cells; p0 += per) {
+                const uint64_t np = std::min(per, cells - p0);
+                hipLaunchKernelGGL(k_rect_compact, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, st, d_c, d_d, N, b0,
+                                   p0, np, out);
+            }
+            HIPC(hipGetLastError());
+            b0 = b1;
+        }
+    }
+    HIPC(hipMemcpyAsync(h_tot, d_count, 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    const uint64_t total = h_tot[0];
+    *n_pairs = total;
+    if (total > cap) {
+        set_error("the pair list holds " + std::to_string(total) + " records, the buffer " + std::to_string(cap));
+        return DREPHIP_ERR_NOMEM;
+    }
+    return DREPHIP_OK;
 }
 
 // Completes a deferred table-path call (drephip_allpairs_device_async): waits

@@ -139,7 +139,7 @@ static int refuse_if_pending(drephip_ctx *ctx) {
     return DREPHIP_ERR_ARG;
 }
 
-DREPHIP_EXPORT int drephip_version(void) { return 300; }
+DREPHIP_EXPORT int drephip_version(void) { return 400; }
 
 #ifndef DREPHIP_SRC_DIGEST
 #define DREPHIP_SRC_DIGEST "unknown"
@@ -1319,6 +1319,152 @@ DREPHIP_EXPORT int drephip_allpairs_sparse(drephip_ctx *ctx, const uint64_t *has
     HIPC(hipMemcpyAsync(d_n, nhash, N * 4ull, hipMemcpyHostToDevice, st));
     timing_begin(ctx);
     rc = allpairs_sparse_impl(ctx, d_h, d_n, N, row0, row1, (uint4 *)d_p, cap, n_pairs, st);
+    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
+    timing_collect(ctx);
+    const uint64_t have = std::min(*n_pairs, cap);
+    if (have) HIPC(hipMemcpyAsync(pairs, d_p, have * 16, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return rc;
+}
+
+// ------------------------------------------------- query against reference
+// `mash dist <reference.msh> <query.msh>`: the Q x N rectangle (allpairs.hip,
+// rect_device_impl / rect_sparse_impl)
+static bool rect_null(const void *a, const void *b, uint32_t Q, const void *c, const void *d, uint32_t N) {
+    return (Q && (!a || !b)) || (N && (!c || !d));
+}
+
+DREPHIP_EXPORT int drephip_dist_rect_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash,
+                                            uint32_t Q, const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N,
+                                            uint32_t q0, uint32_t q1, uint16_t *d_common, uint16_t *d_denom,
+                                            void *stream) {
+    GUARD_CTX(ctx);
+    if (rect_null(d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N) || (Q && N && q0 < q1 && !d_common)) {
+        set_error("null argument");
+        return DREPHIP_ERR_ARG;
+    }
+    timing_begin(ctx);
+    int rc = rect_device_impl(ctx, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1, d_common, d_denom,
+                              pick_stream(ctx, stream), false);
+    if (rc) return rc;
+    timing_collect(ctx);
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_dist_rect_merge_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash,
+                                                  uint32_t Q, const uint64_t *d_rhashes, const uint32_t *d_rnhash,
+                                                  uint32_t N, uint32_t q0, uint32_t q1, uint16_t *d_common,
+                                                  uint16_t *d_denom, void *stream) {
+    GUARD_CTX(ctx);
+    if (rect_null(d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N) || (Q && N && q0 < q1 && !d_common)) {
+        set_error("null argument");
+        return DREPHIP_ERR_ARG;
+    }
+    timing_begin(ctx);
+    int rc = rect_device_impl(ctx, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1, d_common, d_denom,
+                              pick_stream(ctx, stream), true);
+    if (rc) return rc;
+    timing_collect(ctx);
+    return DREPHIP_OK;
+}
+
+// a host sketch matrix as the kernels need it: nhash <= s, rows ascending and
+// distinct, UINT64_MAX past nhash
+static int check_rows(const uint64_t *hashes, const uint32_t *nhash, uint32_t n, uint32_t s) {
+    for (uint32_t i = 0; i < n; i++) {
+        if (nhash[i] > s) { set_error("nhash[i] > s"); return DREPHIP_ERR_ARG; }
+        const uint64_t *row = hashes + (uint64_t)i * s;
+        for (uint32_t j = 1; j < nhash[i]; j++)
+            if (row[j - 1] >= row[j]) { set_error("sketch rows must be ascending and distinct"); return DREPHIP_ERR_ARG; }
+        for (uint32_t j = nhash[i]; j < s; j++)
+            if (row[j] != ~0ull) { set_error("sketch rows must be UINT64_MAX past nhash[i]"); return DREPHIP_ERR_ARG; }
+    }
+    return DREPHIP_OK;
+}
+
+// both matrices of a host rectangle call onto the context's device
+static int rect_stage(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash, uint32_t Q,
+                      const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint64_t **d_qh, uint32_t **d_qn,
+                      uint64_t **d_rh, uint32_t **d_rn) {
+    int rc;
+    const uint32_t s = ctx->s;
+    hipStream_t st = ctx->stream;
+    if ((rc = scratch(ctx, "rect_in_qh", (uint64_t)Q * s * 8, (void **)d_qh))) return rc;
+    if ((rc = scratch(ctx, "rect_in_qn", Q * 4ull, (void **)d_qn))) return rc;
+    if ((rc = scratch(ctx, "rect_in_rh", (uint64_t)N * s * 8, (void **)d_rh))) return rc;
+    if ((rc = scratch(ctx, "rect_in_rn", N * 4ull, (void **)d_rn))) return rc;
+    HIPC(hipMemcpyAsync(*d_qh, qhashes, (uint64_t)Q * s * 8, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(*d_qn, qnhash, Q * 4ull, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(*d_rh, rhashes, (uint64_t)N * s * 8, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(*d_rn, rnhash, N * 4ull, hipMemcpyHostToDevice, st));
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_dist_rect(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash, uint32_t Q,
+                                     const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint32_t q0,
+                                     uint32_t q1, uint16_t *common_out, uint16_t *denom_out) {
+    GUARD_CTX(ctx);
+    if (rect_null(qhashes, qnhash, Q, rhashes, rnhash, N)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    if (q1 > Q) q1 = Q;
+    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
+    if (!common_out) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    int rc;
+    if ((rc = check_rows(qhashes, qnhash, Q, ctx->s)) || (rc = check_rows(rhashes, rnhash, N, ctx->s))) return rc;
+    hipStream_t st = ctx->stream;
+    uint64_t *d_qh, *d_rh;
+    uint32_t *d_qn, *d_rn;
+    uint16_t *d_c, *d_d = nullptr;
+    const uint64_t cells = (uint64_t)(q1 - q0) * N;
+    if ((rc = rect_stage(ctx, qhashes, qnhash, Q, rhashes, rnhash, N, &d_qh, &d_qn, &d_rh, &d_rn))) return rc;
+    if ((rc = scratch(ctx, "rect_out_c", cells * 2, (void **)&d_c))) return rc;
+    if (denom_out && (rc = scratch(ctx, "rect_out_d", cells * 2, (void **)&d_d))) return rc;
+    timing_begin(ctx);
+    if ((rc = rect_device_impl(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, d_c, d_d, st, false))) return rc;
+    timing_collect(ctx);
+    HIPC(hipMemcpyAsync(common_out, d_c, cells * 2, hipMemcpyDeviceToHost, st));
+    if (denom_out) HIPC(hipMemcpyAsync(denom_out, d_d, cells * 2, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_dist_rect_sparse_device(drephip_ctx *ctx, const uint64_t *d_qhashes,
+                                                   const uint32_t *d_qnhash, uint32_t Q, const uint64_t *d_rhashes,
+                                                   const uint32_t *d_rnhash, uint32_t N, uint32_t q0, uint32_t q1,
+                                                   uint32_t *d_pairs, uint64_t cap, uint64_t *n_pairs, void *stream) {
+    GUARD_CTX(ctx);
+    if (rect_null(d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N) || !n_pairs || (cap && !d_pairs)) {
+        set_error("null argument");
+        return DREPHIP_ERR_ARG;
+    }
+    timing_begin(ctx);
+    int rc = rect_sparse_impl(ctx, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1, (uint4 *)d_pairs, cap,
+                              n_pairs, pick_stream(ctx, stream));
+    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
+    timing_collect(ctx);
+    return rc;
+}
+
+DREPHIP_EXPORT int drephip_dist_rect_sparse(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash,
+                                            uint32_t Q, const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N,
+                                            uint32_t q0, uint32_t q1, uint32_t *pairs, uint64_t cap,
+                                            uint64_t *n_pairs) {
+    GUARD_CTX(ctx);
+    if (rect_null(qhashes, qnhash, Q, rhashes, rnhash, N) || !n_pairs || (cap && !pairs)) {
+        set_error("null argument");
+        return DREPHIP_ERR_ARG;
+    }
+    *n_pairs = 0;
+    if (q1 > Q) q1 = Q;
+    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
+    int rc;
+    if ((rc = check_rows(qhashes, qnhash, Q, ctx->s)) || (rc = check_rows(rhashes, rnhash, N, ctx->s))) return rc;
+    hipStream_t st = ctx->stream;
+    uint64_t *d_qh, *d_rh;
+    uint32_t *d_qn, *d_rn, *d_p = nullptr;
+    if ((rc = rect_stage(ctx, qhashes, qnhash, Q, rhashes, rnhash, N, &d_qh, &d_qn, &d_rh, &d_rn))) return rc;
+    if (cap && (rc = scratch(ctx, "rect_sp_out", cap * 16, (void **)&d_p))) return rc;
+    timing_begin(ctx);
+    rc = rect_sparse_impl(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, (uint4 *)d_p, cap, n_pairs, st);
     if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
     timing_collect(ctx);
     const uint64_t have = std::min(*n_pairs, cap);

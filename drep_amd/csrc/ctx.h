@@ -313,6 +313,19 @@ int allpairs_sparse_list_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const 
                               const SparseOut &out, hipStream_t st);
 uint64_t allpairs_image_bytes_per_row(drephip_ctx *ctx, uint32_t R);
 
+// Query against reference (allpairs.hip): rows [q0, q1) of the Q x N rectangle
+// of the query matrix against the reference matrix, row-major, by the RECT
+// flavour of the whole-row kernel or (force_merge, s > 2048, DREPHIP_AP_MERGE)
+// k_rect_merge.  Blocking.
+int rect_device_impl(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
+                     const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0, uint32_t q1,
+                     uint16_t *d_common, uint16_t *d_denom, hipStream_t st, bool force_merge);
+// The same rows as records {q, r, common, denom} of the pairs with common > 0
+// (the contract of allpairs_sparse_impl).  Blocking.
+int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
+                     const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0, uint32_t q1,
+                     uint4 *d_pairs, uint64_t cap, uint64_t *n_pairs, hipStream_t st);
+
 // Primary clustering (linkage.hip).
 int linkage_device_impl(drephip_ctx *ctx, double *d_D, uint32_t n, int method, double *Z_out, hipStream_t st);
 int dist_matrix_impl(drephip_ctx *ctx, const uint16_t *d_common, const uint16_t *d_denom, uint32_t n,

@@ -831,3 +831,260 @@ def mdb_from_sparse(sm: SparseMash, k: int = MASH_K) -> pd.DataFrame:
     return pd.DataFrame({'genome1': pd.Categorical.from_codes(codes[r[order]], dtype=dtype, validate=False),
                          'genome2': pd.Categorical.from_codes(codes[q[order]], dtype=dtype, validate=False),
                          'dist': dist, 'similarity': np.float32(1) - dist}, index=t[order], copy=False)
+
+
+# ------------------------------------------------- query against reference
+# `mash dist <reference.msh> <query.msh>`, the two-file form of the call at
+# drep/d_cluster.py:569-573: new genomes against a sketch database that an
+# earlier all_vs_all_MASH run left behind, without redoing reference x reference.
+@dataclass
+class RectMash:
+    qnames: List[str]          # queries (basename), Qdb order
+    qlocations: List[str]
+    rnames: List[str]          # references (basename), order of the .msh file
+    rlocations: List[str]      # their names as the .msh file holds them
+    common: Optional[np.ndarray]   # uint16 [Q, N] (dense form), else None
+    denom: Optional[np.ndarray]    # uint16 [Q, N]
+    q: Optional[np.ndarray]        # record form: uint32 query rows, sorted by (q, r); else None
+    r: Optional[np.ndarray]        # uint32 reference rows
+    rec_common: Optional[np.ndarray]   # uint16, > 0
+    rec_denom: Optional[np.ndarray]    # uint16
+    qnhash: np.ndarray
+    rnhash: np.ndarray
+    qlength: np.ndarray
+    rlength: np.ndarray
+    s: int
+
+
+def _query_ranges(Q: int, n: int) -> List[tuple]:
+    """Q query rows in n contiguous ranges of near-equal size (every row of
+    the rectangle costs the same: N pairs)."""
+    return [(Q * k // n, Q * (k + 1) // n) for k in range(n)]
+
+
+def rect_allpairs(qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray, s: int,
+                  devices: Sequence[int] = (0,)):
+    """(common[Q, N], denom[Q, N]) of `mash dist <reference> <query>`: every
+    query sketch against every reference sketch (libdrephip
+    drephip_dist_rect).  With several devices the query rows are split into
+    contiguous ranges, one context and host thread per device, each writing
+    its own rows of the host buffers, as condensed_allpairs splits the
+    triangle.  denom is always filled.  ValueError for mismatched dtypes or
+    shapes, before any GPU call."""
+    qhashes, qnhash, rhashes, rnhash = _lib.rect_arrays(qhashes, qnhash, rhashes, rnhash, s)
+    Q, N = len(qnhash), len(rnhash)
+    common = np.zeros((Q, N), dtype=np.uint16)
+    denom = np.zeros((Q, N), dtype=np.uint16)
+    parts = _query_ranges(Q, len(devices))
+
+    def run(k, dev):
+        a, b = parts[k]
+        if b <= a:
+            return
+        with _lib.Context(device=dev, k=MASH_K, s=s, seed=MASH_SEED) as ctx:
+            ctx.dist_rect(qhashes, qnhash, rhashes, rnhash, a, b, common[a:b], denom[a:b])
+    if Q and N:
+        _on_devices(list(devices), run)
+    return common, denom
+
+
+def rect_allpairs_sparse(qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray, s: int,
+                         devices: Sequence[int] = (0,)):
+    """(q, r, common, denom) of the (query, reference) pairs sharing a hash,
+    sorted by (q, r) (libdrephip drephip_dist_rect_sparse); query rows split
+    over the devices as rect_allpairs splits them."""
+    qhashes, qnhash, rhashes, rnhash = _lib.rect_arrays(qhashes, qnhash, rhashes, rnhash, s)
+    Q, N = len(qnhash), len(rnhash)
+    none = tuple(np.zeros(0, t) for t in (np.uint32, np.uint32, np.uint16, np.uint16))
+    parts = _query_ranges(Q, len(devices))
+
+    def run(k, dev):
+        a, b = parts[k]
+        if b <= a:
+            return none
+        with _lib.Context(device=dev, k=MASH_K, s=s, seed=MASH_SEED) as ctx:
+            return ctx.dist_rect_sparse(qhashes, qnhash, rhashes, rnhash, a, b)
+    if not (Q and N):
+        return none
+    res = _on_devices(list(devices), run)
+    return tuple(np.concatenate([x[k] for x in res]) for k in range(4))
+
+
+_MAX_SKETCH = 32767      # drephip_max_sketch(): counts and denominators are uint16
+
+
+def _read_reference(path: str, kwargs):
+    """The reference .msh of a query call: (names, locations, hashes, nhash,
+    length, s).  It must be a k = 21, seed 42 sketch file of one sketch size,
+    which is the call's s; a MASH_sketch kwarg that differs raises."""
+    m = read_msh(path)
+    if m.kmer != MASH_K or m.seed != MASH_SEED:
+        raise ValueError("%s: reference sketches must have k = %d and seed %d, got k = %d, seed %d"
+                         % (path, MASH_K, MASH_SEED, m.kmer, m.seed))
+    s = int(m.sketch_size)
+    if s < 1 or s > _MAX_SKETCH or any(len(ref.hashes) > s for ref in m.references):
+        raise ValueError("%s: reference sketches must share one sketch size in 1..%d" % (path, _MAX_SKETCH))
+    if 'MASH_sketch' in kwargs and int(kwargs['MASH_sketch']) != s:
+        raise ValueError("MASH_sketch = %s, but the reference %s was sketched with s = %d"
+                         % (kwargs['MASH_sketch'], path, s))
+    N = len(m.references)
+    hashes = np.full((N, s), np.iinfo(np.uint64).max, dtype=np.uint64)
+    nhash = np.zeros(N, dtype=np.uint32)
+    length = np.zeros(N, dtype=np.uint64)
+    for i, ref in enumerate(m.references):
+        n = len(ref.hashes)
+        hashes[i, :n] = ref.hashes
+        nhash[i] = n
+        length[i] = ref.length
+    locations = [ref.name for ref in m.references]
+    return [_get_genome_name_from_fasta(x) for x in locations], locations, hashes, nhash, length, s
+
+
+def _rect_distance64(common: np.ndarray, denom: np.ndarray, k: int = MASH_K) -> np.ndarray:
+    """float64 Mash distance per (common, denom) (drephip_distance_lut)."""
+    common, denom = np.asarray(common), np.asarray(denom)
+    out = np.zeros(common.shape, dtype=np.float64)       # denominator 0 (two empty sketches): 0
+    for d in np.unique(denom):
+        if int(d) == 0:
+            continue
+        sel = denom == d
+        out[sel] = _lib.distance_lut(int(d), k)[common[sel]]
+    return out
+
+
+def query_vs_MASH_rect(Qdb, data_folder, reference=None, **kwargs) -> RectMash:
+    """The genomes of Qdb against a reference sketch file: the counts behind
+    `mash dist <reference.msh> <query.msh>` (the two-file form of
+    drep/d_cluster.py:569-573).
+
+    reference: a .msh path; default <data_folder>/MASH_files/ALL.msh, the file
+    every earlier all_vs_all_MASH run left there.  It must hold k = 21, seed 42
+    sketches of one size, which becomes the call's s (a differing MASH_sketch
+    kwarg raises ValueError).  The queries are sketched (or loaded from their
+    cache) by sketch_genomes into kwargs['query_folder'] (default
+    <data_folder>/MASH_query), so <data_folder>/MASH_files is never modified.
+    max_dist (default None: the dense Q x N form): the record form, only the
+    pairs that share a hash.  gpu, gpus, processors and ingest as in
+    all_vs_all_MASH."""
+    _check_ingest(kwargs)
+    max_dist = kwargs.get('max_dist', None)
+    if max_dist is not None and not (0 <= float(max_dist) < 1):
+        raise ValueError("max_dist must be in [0, 1): the record form lists only pairs that share a hash")
+    if reference is None:
+        reference = os.path.join(data_folder, 'MASH_files', 'ALL.msh')
+    rnames, rlocs, rh, rn, rlen, s = _read_reference(reference, kwargs)
+    qfolder = kwargs.get('query_folder', os.path.join(data_folder, 'MASH_query'))
+    skw = {k: v for k, v in kwargs.items() if k not in ('query_folder', 'max_dist')}
+    skw['MASH_sketch'] = s
+    sk = sketch_genomes(Qdb, qfolder, **skw)
+    devs = _devices(kwargs)
+    with _Stage('rect_s'):
+        if max_dist is None:
+            common, denom = rect_allpairs(sk.hashes, sk.nhash, rh, rn, s, devs)
+            rec = (None, None, None, None)
+        else:
+            common = denom = None
+            rec = rect_allpairs_sparse(sk.hashes, sk.nhash, rh, rn, s, devs)
+    return RectMash(sk.names, sk.locations, rnames, rlocs, common, denom, rec[0], rec[1], rec[2], rec[3],
+                    sk.nhash, rn, sk.length, rlen, s)
+
+
+def mdb_from_rect(rm: RectMash, k: int = MASH_K, max_dist: Optional[float] = None) -> pd.DataFrame:
+    """The table dRep's parse (drep/d_cluster.py:575-585) makes of `mash dist
+    <reference> <queries>`: rows query-outer, reference-inner; genome1 the
+    reference name, genome2 the query name, each an ordered categorical over
+    that side's sorted names; dist float32 through the %g / read_csv route
+    (float32_tables), similarity = 1 - dist.  The record form gives the rows of
+    the listed pairs (plus empty query against empty reference, distance 0 to
+    Mash), in the same order; max_dist keeps the rows whose float64 Mash
+    distance (drephip_distance_lut) is <= max_dist."""
+    Q, N = len(rm.qnames), len(rm.rnames)
+    if rm.common is not None:
+        q = np.repeat(np.arange(Q, dtype=np.int64), N)
+        r = np.tile(np.arange(N, dtype=np.int64), Q)
+        c = np.asarray(rm.common, dtype=np.uint16).reshape(-1)
+        d = np.asarray(rm.denom, dtype=np.uint16).reshape(-1)
+    else:
+        q, r = np.asarray(rm.q, dtype=np.int64), np.asarray(rm.r, dtype=np.int64)
+        c, d = np.asarray(rm.rec_common, dtype=np.uint16), np.asarray(rm.rec_denom, dtype=np.uint16)
+        eq = np.nonzero(np.asarray(rm.qnhash) == 0)[0]
+        er = np.nonzero(np.asarray(rm.rnhash) == 0)[0]
+        if len(eq) and len(er):
+            q = np.concatenate([q, np.repeat(eq, len(er))])
+            r = np.concatenate([r, np.tile(er, len(eq))])
+            c = np.concatenate([c, np.zeros(len(eq) * len(er), np.uint16)])
+            d = np.concatenate([d, np.zeros(len(eq) * len(er), np.uint16)])
+            order = np.argsort(q * max(N, 1) + r, kind='stable')
+            q, r, c, d = q[order], r[order], c[order], d[order]
+    if max_dist is not None:
+        keep = _rect_distance64(c, d, k) <= float(max_dist)
+        q, r, c, d = q[keep], r[keep], c[keep], d[keep]
+    dens = np.unique(d) if len(d) else np.array([rm.s])
+    lut32, lut_off = float32_tables(dens, rm.s, k)
+    dist = lut32[lut_off[d.astype(np.int64)].astype(np.int64) + c.astype(np.int64)].astype(np.float32) if len(d) \
+        else np.zeros(0, np.float32)
+
+    def cat(names, idx):
+        cats = sorted(set(names))
+        dtype = pd.CategoricalDtype(cats, ordered=True)
+        code_t = pd.Categorical([], dtype=dtype).codes.dtype
+        pos = {n: x for x, n in enumerate(cats)}
+        codes = np.array([pos[n] for n in names], dtype=code_t)
+        return pd.Categorical.from_codes(codes[idx] if len(codes) else np.zeros(0, code_t), dtype=dtype, validate=False)
+    return pd.DataFrame({'genome1': cat(rm.rnames, r), 'genome2': cat(rm.qnames, q),
+                         'dist': dist, 'similarity': np.float32(1) - dist}, copy=False)
+
+
+def query_vs_MASH(Qdb, data_folder, reference=None, **kwargs):
+    """`mash dist <reference.msh> <queries>` parsed as dRep parses its table
+    (drep/d_cluster.py:569-585), with sketching and the distances on the GPU:
+    the genomes of Qdb (genome, location) against the reference sketches.
+
+    Args and keyword args as query_vs_MASH_rect.  max_dist (default None: all
+    Q x N rows): only the rows whose float64 Mash distance is <= max_dist,
+    from the record form of the kernel.  This is this library's own filter:
+    Mash's -d option cannot be pinned here, because no Mash binary is available
+    to compare against.
+
+    Returns:
+        DataFrame [genome1 (reference), genome2 (query), dist, similarity],
+        rows query-outer, reference-inner
+    """
+    rm = query_vs_MASH_rect(Qdb, data_folder, reference, **kwargs)
+    with _Stage('mdb_s'):
+        return mdb_from_rect(rm, max_dist=kwargs.get('max_dist', None))
+
+
+def union_condensed(cm_ref: CondensedMash, rm: RectMash, cm_query: CondensedMash) -> CondensedMash:
+    """The condensed triangle of (references, then queries) from the
+    references' triangle, the query x reference rectangle and the queries'
+    triangle: extends a stored run by new genomes for cluster_mash_condensed
+    without redoing reference x reference.  Pure numpy."""
+    Nr, Nq = len(cm_ref.names), len(cm_query.names)
+    if rm.common is None:
+        raise ValueError("union_condensed needs the dense form of the rectangle")
+    if not (cm_ref.s == rm.s == cm_query.s):
+        raise ValueError("the three parts must share one sketch size")
+    if list(rm.rnames) != list(cm_ref.names) or list(rm.qnames) != list(cm_query.names):
+        raise ValueError("the rectangle's reference / query names must be the two triangles' names, in order")
+    rc, rd = np.asarray(rm.common), np.asarray(rm.denom)
+    if rc.shape != (Nq, Nr) or rd.shape != (Nq, Nr):
+        raise ValueError("the rectangle must be [queries, references] = [%d, %d]" % (Nq, Nr))
+    N = Nr + Nq
+    out = []
+    for src_ref, src_q, rect in ((cm_ref.common, cm_query.common, rc), (cm_ref.denom, cm_query.denom, rd)):
+        src_ref, src_q = np.asarray(src_ref, dtype=np.uint16), np.asarray(src_q, dtype=np.uint16)
+        v = np.empty(N * (N - 1) // 2, dtype=np.uint16)
+        rect_t = np.ascontiguousarray(rect.T, dtype=np.uint16)       # [references, queries]
+        pos = 0
+        for i in range(Nr):                                          # row i: its references, then every query
+            a, n = cond_start(i, Nr), Nr - 1 - i
+            v[pos:pos + n] = src_ref[a:a + n]
+            pos += n
+            v[pos:pos + Nq] = rect_t[i]
+            pos += Nq
+        v[pos:] = src_q                                              # the queries' rows: their own triangle
+        out.append(v)
+    return CondensedMash(list(cm_ref.names) + list(cm_query.names), list(cm_ref.locations) + list(cm_query.locations),
+                         out[0], out[1], np.concatenate([np.asarray(cm_ref.nhash), np.asarray(cm_query.nhash)]),
+                         np.concatenate([np.asarray(cm_ref.length), np.asarray(cm_query.length)]), cm_ref.s)

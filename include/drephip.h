@@ -469,6 +469,62 @@ int drephip_allpairs_sparse(drephip_ctx *ctx, const uint64_t *hashes, const uint
 int drephip_last_sparse_stats(drephip_ctx *ctx, uint32_t *blocks, uint64_t *direct, uint64_t *fallback,
                               uint64_t *scratch_bytes);
 
+/* ------------------------------------------------- query against reference
+ * Replaces: `mash dist <reference.msh> <query.msh>`, the two-file form of the
+ * call at drep/d_cluster.py:569-573 (which passes ALL.msh twice): Q query
+ * sketches against N reference sketches, both matrices of s hashes per row as
+ * the dist section above requires them.  The result is the Q x N rectangle of
+ * (common, denom), defined as in that section: denominator s when both
+ * sketches are full, else min(s, |A u B|).  There is no diagonal: a query that
+ * is also a reference meets itself (common = denom = its hash count; 0 / 0 for
+ * two empty sketches), as the self rows of Mash's table do.
+ *
+ * drephip_dist_rect_device: rows [q0, q1) of the rectangle (q1 clamped to Q);
+ * d_common / d_denom hold (q1 - q0) x N entries, row-major -- pair (q, r) at
+ * (q - q0) * N + r -- and nothing else is written; d_denom may be NULL.
+ * Q == 0, N == 0 or q0 >= q1: DREPHIP_OK, nothing written.  Null pointers:
+ * DREPHIP_ERR_ARG.  Kernels: the RECT flavour of k_allpairs_q (whole-row LDS
+ * tables of the query rows, the reference sketches streamed as columns) for
+ * s <= 2048 (DREPHIP_AP_AUTO / DREPHIP_AP_TABLE), k_rect_merge (the literal
+ * merge, one lane per pair) above and for DREPHIP_AP_MERGE; a context set to
+ * DREPHIP_AP_BAND gets DREPHIP_ERR_UNSUPPORTED (no RECT band kernel).  No
+ * shared-hash screen runs.  Blocking, on the caller's stream; a pending
+ * drephip_allpairs_device_async on the context is waited for first.
+ * drephip_last_kernel_ms `which` 2 / 3 report the rectangle's kernel and its
+ * table build.  The device forms assume well-formed rows. */
+int drephip_dist_rect_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
+                             const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0,
+                             uint32_t q1, uint16_t *d_common, uint16_t *d_denom /* nullable */, void *stream);
+/* The same rectangle by k_rect_merge whatever s (`mash dist <reference.msh>
+ * <query.msh>` by Mash's own loop): the independent cross-check. */
+int drephip_dist_rect_merge_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
+                                   const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0,
+                                   uint32_t q1, uint16_t *d_common, uint16_t *d_denom /* nullable */, void *stream);
+/* The host form of `mash dist <reference.msh> <query.msh>`: both matrices are
+ * staged on the context's device and checked first (every row ascending and
+ * distinct, nhash <= s, UINT64_MAX past nhash; DREPHIP_ERR_ARG otherwise). */
+int drephip_dist_rect(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash, uint32_t Q,
+                      const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint32_t q0, uint32_t q1,
+                      uint16_t *common_out, uint16_t *denom_out /* nullable */);
+/* `mash dist <reference.msh> <query.msh>` listing only the pairs that share a
+ * hash: records of 4 uint32 {q, r, common, denom} (q the query row, r the
+ * reference row), common > 0, each pair at most once, order unspecified.  The
+ * cap / n_pairs contract is that of drephip_allpairs_sparse_device: cap = 0
+ * only counts; with too few slots only [0, cap) is written, the call returns
+ * DREPHIP_ERR_NOMEM and *n_pairs is the size needed.  s <= 2048: the RECT
+ * kernel stages and appends the records itself, no rectangle is written.
+ * Above, and for DREPHIP_AP_MERGE: query-row blocks of at most 2^28 pairs,
+ * each merged into a scratch rectangle of the context and compacted. */
+int drephip_dist_rect_sparse_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
+                                    const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0,
+                                    uint32_t q1, uint32_t *d_pairs /* cap x 4 */, uint64_t cap, uint64_t *n_pairs,
+                                    void *stream);
+/* The host form of the record call (`mash dist <reference.msh> <query.msh>`,
+ * non-zero pairs only); both matrices checked as drephip_dist_rect does. */
+int drephip_dist_rect_sparse(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash, uint32_t Q,
+                             const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint32_t q0, uint32_t q1,
+                             uint32_t *pairs /* cap x 4 */, uint64_t cap, uint64_t *n_pairs);
+
 /* ---------------------------------------------------------- primary clustering
  * Replaces: scipy.cluster.hierarchy.linkage(squareform(dist), method) in
  * cluster_hierarchical (drep/d_cluster.py:447-453), called from
