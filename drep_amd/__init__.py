@@ -13,7 +13,8 @@ from ._lib import Context, DrepHipError
 
 __all__ = ["Context", "DrepHipError", "mash_io", "d_cluster", "SparseMash", "all_vs_all_MASH_sparse",
            "cluster_mash_sparse", "mdb_from_sparse", "store_sparse", "load_sparse", "RectMash", "query_vs_MASH",
-           "query_vs_MASH_rect", "rect_allpairs", "rect_allpairs_sparse", "mdb_from_rect", "union_condensed"]
+           "query_vs_MASH_rect", "rect_allpairs", "rect_allpairs_sparse", "mdb_from_rect", "union_condensed",
+           "rect_top_hits", "query_best_hits", "place_queries"]
 __version__ = "0.1.0"
 
 
@@ -25,7 +26,7 @@ def __getattr__(name):
         import importlib           # the sparse pipeline (>~2x10^5 genomes), lazy for the same reason
         return getattr(importlib.import_module(".d_cluster", __name__), name)
     if name in ("RectMash", "query_vs_MASH", "query_vs_MASH_rect", "rect_allpairs", "rect_allpairs_sparse",
-                "mdb_from_rect", "union_condensed"):
+                "mdb_from_rect", "union_condensed", "rect_top_hits", "query_best_hits", "place_queries"):
         import importlib           # query against reference (`mash dist <reference> <query>`)
         return getattr(importlib.import_module(".d_cluster", __name__), name)
     if name in ("store_sparse", "load_sparse"):

@@ -104,6 +104,10 @@ SIGNATURES = {
                                                   vp, C.c_uint64, C.POINTER(C.c_uint64), vp]),
     "drephip_dist_rect_sparse": (C.c_int, [vp, u64p, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint32,
                                            C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "drephip_dist_rect_top_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.c_uint32, vp, vp, vp]),
+    "drephip_dist_rect_top": (C.c_int, [vp, u64p, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.c_uint32, vp, vp]),
     "drephip_last_sparse_stats": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint64)]),
     "drephip_distance_lut": (C.c_int, [C.c_int, C.c_uint32, f64p]),
@@ -922,6 +926,52 @@ class Context:
         rec = rec[np.lexsort((rec[:, 1], rec[:, 0]))]
         return (np.ascontiguousarray(rec[:, 0]), np.ascontiguousarray(rec[:, 1]),
                 rec[:, 2].astype(np.uint16), rec[:, 3].astype(np.uint16))
+
+    def dist_rect_top_raw(self, qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray,
+                          top: int, q0: int, q1: Optional[int], hits: np.ndarray, count: np.ndarray) -> int:
+        """One drephip_dist_rect_top call into `hits` (contiguous uint32, at
+        least rows * top * 4 entries) and `count` (contiguous uint32, at least
+        rows entries), rows = q1 - q0 after clamping; returns rows.  Only the
+        rows' slots are written."""
+        qhashes, qnhash, rhashes, rnhash = rect_arrays(qhashes, qnhash, rhashes, rnhash, self.s)
+        Q, N = len(qnhash), len(rnhash)
+        q0, q1 = self._rect_range(Q, q0, q1)
+        rows, top = max(0, q1 - q0), int(top)
+        for arr, need in ((hits, rows * max(top, 0) * 4), (count, rows)):
+            if arr.dtype != np.uint32 or not arr.flags.c_contiguous or arr.size < need:
+                raise ValueError("output buffers must be contiguous uint32 of at least %d entries" % need)
+        if top < 0:
+            raise ValueError("top must not be negative")
+        check(lib().drephip_dist_rect_top(self._h, qhashes.reshape(-1), qnhash, Q, rhashes.reshape(-1), rnhash, N,
+                                          q0, q1, top, hits.ctypes.data, count.ctypes.data), "drephip_dist_rect_top")
+        return rows
+
+    def dist_rect_top(self, qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray,
+                      top: int, q0: int = 0, q1: Optional[int] = None):
+        """The `top` (1..64) nearest references of query rows [q0, q1) among
+        those sharing a hash with the row (drephip_dist_rect_top): (ref int64
+        [rows, top], common uint16 [rows, top], denom uint16 [rows, top], count
+        uint32 [rows]).  Nearest first: larger common / denom as exact
+        rationals, ties by the smaller reference row.  Slots at or past
+        count[row] hold ref -1, common 0, denom 0."""
+        Q = len(np.asarray(qnhash))
+        a, b = self._rect_range(Q, q0, q1)
+        rows, top = max(0, b - a), int(top)
+        hits = np.empty((rows, max(top, 0), 4), dtype=np.uint32)
+        hits[:] = (0xFFFFFFFF, 0, 0, 0)                  # (an empty call writes nothing)
+        count = np.zeros(rows, dtype=np.uint32)
+        self.dist_rect_top_raw(qhashes, qnhash, rhashes, rnhash, top, q0, q1, hits, count)
+        ref = hits[:, :, 0].astype(np.int64)
+        ref[ref == 0xFFFFFFFF] = -1
+        return ref, hits[:, :, 1].astype(np.uint16), hits[:, :, 2].astype(np.uint16), count
+
+    def dist_rect_top_device(self, d_qhashes: int, d_qnhash: int, Q: int, d_rhashes: int, d_rnhash: int, N: int,
+                             q0: int, q1: int, top: int, d_hits: Optional[int], d_count: Optional[int],
+                             stream: Optional[int] = None) -> None:
+        """drephip_dist_rect_top_device: d_hits uint32 [(q1 - q0), top, 4],
+        d_count uint32 [q1 - q0], device pointers."""
+        check(lib().drephip_dist_rect_top_device(self._h, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1,
+                                                 int(top), d_hits, d_count, stream), "drephip_dist_rect_top_device")
 
     def sparse_stats(self) -> dict:
         """{blocks, direct, fallback, scratch_bytes} of the last sparse all-pairs call."""

@@ -1980,6 +1980,102 @@ __global__ __launch_bounds__(256) void k_rect_compact(const uint16_t *__restrict
     if (c) sparse_append(sp, q0 + (uint32_t)(cell / N), (uint32_t)(cell % N), c, denom[cell]);
 }
 
+// Best hits (drephip_dist_rect_top_device): the `top` nearest references of
+// every row of a block's scratch rectangle.  Nearest = largest common / denom
+// (the Mash distance falls strictly with it), ties to the smaller r; as one
+// 64-bit key, larger first:
+//   floor(common * (2^32 - 1) / denom) << 32 | ~r
+// Two different ratios with denominators below 2^15 differ by more than 2^-30,
+// so their 32-bit quotients differ and keep their order; equal ratios give
+// equal quotients.  No cell with common > 0 has key 0, the empty slot.
+constexpr uint32_t kTopWG = 256;
+constexpr uint32_t kTopVec = 8;                    // cells per lane per step: one 16-byte load of common
+constexpr uint32_t kTopStep = kTopWG * kTopVec;    // cells per workgroup step
+constexpr uint32_t kTopList = 4096;                // keys of the LDS list (32 KB): two steps' worth
+
+__device__ __forceinline__ uint64_t top_key(uint32_t c, uint32_t d, uint32_t r) {
+    return (((uint64_t)c * 0xFFFFFFFFull / d) << 32) | (uint32_t)~r;
+}
+
+// list[0, have) sorted largest first (a bitonic sort of the next power of two,
+// the tail padded with empty slots); every thread of the workgroup calls it
+__device__ void top_sort(uint64_t *list, uint32_t have) {
+    uint32_t n = 2;
+    while (n < have) n <<= 1;
+    for (uint32_t t = have + threadIdx.x; t < n; t += kTopWG) list[t] = 0;
+    for (uint32_t k = 2; k <= n; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+            for (uint32_t t = threadIdx.x; t < n / 2; t += kTopWG) {
+                const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;    // the pair that differs in bit j
+                const uint64_t a = list[i], b = list[p];
+                if ((i & k) == 0 ? a < b : a > b) { list[i] = b; list[p] = a; }
+            }
+        }
+    __syncthreads();
+}
+
+// One workgroup per row (rows strided over the grid): the row is streamed in
+// steps of kTopStep cells, 8 per lane by one 16-byte load from the 16-byte
+// boundary at or below the row's first cell (cells of the neighbouring rows are
+// masked; the rectangle is allocated 16 bytes long for the last row's tail),
+// the non-zero cells' keys appended to the LDS list.  Nearly every cell is
+// zero, so the list seldom fills; when the next step could overflow it, it is
+// sorted and cut to its `top` largest -- the top of a union is the top of the
+// parts' tops, so a row of any length stays exact.  The final sort's first
+// `top` keys are the hits; their counts are read back from the rectangle.
+__global__ __launch_bounds__(kTopWG) void k_rect_top(const uint16_t *__restrict__ common,
+                                                     const uint16_t *__restrict__ denom, uint32_t N, uint32_t nrows,
+                                                     uint32_t top, uint32_t *__restrict__ hits,
+                                                     uint32_t *__restrict__ count) {
+    __shared__ uint64_t list[kTopList];
+    __shared__ uint32_t s_have;
+    for (uint32_t row = blockIdx.x; row < nrows; row += gridDim.x) {
+        const uint64_t g0 = (uint64_t)row * N, g1 = g0 + N;
+        if (threadIdx.x == 0) s_have = 0;
+        __syncthreads();
+        for (uint64_t v0 = g0 & ~(uint64_t)(kTopVec - 1); v0 < g1; v0 += kTopStep) {
+            const uint32_t have = s_have;
+            __syncthreads();                            // all have read it before anyone appends
+            if (have + kTopStep > kTopList) {
+                top_sort(list, have);
+                if (threadIdx.x == 0) s_have = std::min(have, top);
+                __syncthreads();
+            }
+            const uint64_t v = v0 + (uint64_t)threadIdx.x * kTopVec;
+            if (v < g1) {
+                const uint4 cw = *reinterpret_cast<const uint4 *>(common + v);
+                if (cw.x | cw.y | cw.z | cw.w) {
+                    const uint4 dw = *reinterpret_cast<const uint4 *>(denom + v);
+                    const uint32_t c2[4] = {cw.x, cw.y, cw.z, cw.w}, d2[4] = {dw.x, dw.y, dw.z, dw.w};
+#pragma unroll
+                    for (uint32_t e = 0; e < kTopVec; e++) {
+                        const uint32_t c = (c2[e / 2] >> (16 * (e & 1))) & 0xFFFFu;
+                        const uint32_t d = (d2[e / 2] >> (16 * (e & 1))) & 0xFFFFu;
+                        const uint64_t cell = v + e;
+                        if (c && cell >= g0 && cell < g1) list[atomicAdd(&s_have, 1u)] = top_key(c, d, (uint32_t)(cell - g0));
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        const uint32_t have = s_have;
+        top_sort(list, have);
+        const uint32_t n = std::min(have, top);
+        if (threadIdx.x < top) {
+            uint32_t *h = hits + ((uint64_t)row * top + threadIdx.x) * 4;
+            if (threadIdx.x < n) {
+                const uint32_t r = ~(uint32_t)list[threadIdx.x];
+                h[0] = r; h[1] = common[g0 + r]; h[2] = denom[g0 + r]; h[3] = 0;
+            } else {
+                h[0] = 0xFFFFFFFFu; h[1] = 0; h[2] = 0; h[3] = 0;
+            }
+        }
+        if (threadIdx.x == 0) count[row] = n;
+        __syncthreads();                                // the list and s_have are the next row's
+    }
+}
+
 static int launch_rect_merge(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, const uint64_t *d_rh,
                              const uint32_t *d_rn, uint32_t N, uint32_t q0, uint64_t cells, uint16_t *d_common,
                              uint16_t *d_denom, hipStream_t st) {
@@ -2221,6 +2317,48 @@ int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_q
     if (total > cap) {
         set_error("the pair list holds " + std::to_string(total) + " records, the buffer " + std::to_string(cap));
         return DREPHIP_ERR_NOMEM;
+    }
+    return DREPHIP_OK;
+}
+
+int rect_top_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
+                  const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint32_t top, uint32_t *d_hits,
+                  uint32_t *d_count, hipStream_t st) {
+    if (ctx->apend.active) {
+        int rc = allpairs_wait_impl(ctx);
+        if (rc) return rc;
+    }
+    if (q1 > Q) q1 = Q;
+    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
+    uint32_t R;
+    int path, rc;
+    if ((rc = rect_path(ctx, false, &R, &path))) return rc;
+    ctx->last_screen = ScreenResult{};
+    // query-row blocks of at most kRectBlockPairs cells (at least one row), as
+    // the record form's merge route; DREPHIP_RECT_TOP_BLOCK_ROWS: fewer (tests)
+    uint32_t rows = (uint32_t)std::max<uint64_t>(1, kRectBlockPairs / N);
+    if (const char *e = getenv("DREPHIP_RECT_TOP_BLOCK_ROWS"))
+        if (atoi(e) > 0) rows = std::min<uint32_t>(rows, (uint32_t)atoi(e));
+    const uint64_t bcells = (uint64_t)std::min<uint32_t>(rows, q1 - q0) * N;
+    uint16_t *d_c, *d_d;
+    // 16 bytes more: k_rect_top reads whole 16-byte words up to the last row's end
+    if ((rc = scratch(ctx, "rect_blk_common", bcells * 2 + 16, (void **)&d_c))) return rc;
+    if ((rc = scratch(ctx, "rect_blk_denom", bcells * 2 + 16, (void **)&d_d))) return rc;
+    for (uint32_t b0 = q0; b0 < q1;) {
+        const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
+        std::vector<ItemGroup> groups;               // lives until the block's stream sync
+        if (path == DREPHIP_AP_MERGE)
+            rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, (uint64_t)(b1 - b0) * N, d_c, d_d, st);
+        else
+            rc = rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, d_c, d_d, nullptr, groups, st);
+        if (rc) return rc;
+        timing_mark(ctx, 5, st, true);
+        hipLaunchKernelGGL(k_rect_top, dim3((uint32_t)std::min<uint64_t>(b1 - b0, max_blocks(kTopWG))), dim3(kTopWG), 0, st,
+                           d_c, d_d, N, b1 - b0, top, d_hits + (uint64_t)(b0 - q0) * top * 4, d_count + (b0 - q0));
+        timing_mark(ctx, 5, st, false);
+        HIPC(hipGetLastError());
+        HIPC(hipStreamSynchronize(st));
+        b0 = b1;
     }
     return DREPHIP_OK;
 }

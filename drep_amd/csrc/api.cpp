@@ -77,7 +77,7 @@ int pinned_host(drephip_ctx *ctx, const char *name, size_t bytes, void **out) {
 }
 
 void timing_begin(drephip_ctx *ctx) {
-    for (int i = 0; i < 5; i++) { ctx->kms[i] = 0; ctx->kn[i] = 0; }
+    for (int i = 0; i < 6; i++) { ctx->kms[i] = 0; ctx->kn[i] = 0; }
     ctx->spans.clear();
     ctx->ev_used = 0;
 }
@@ -215,7 +215,7 @@ DREPHIP_EXPORT int drephip_destroy(drephip_ctx *ctx) {
 
 DREPHIP_EXPORT int drephip_set_timing(drephip_ctx *ctx, int kernels) {
     if (!ctx) { set_error("null context"); return DREPHIP_ERR_ARG; }
-    ctx->timing = (uint32_t)kernels & 0x1Fu;
+    ctx->timing = (uint32_t)kernels & 0x3Fu;
     return DREPHIP_OK;
 }
 
@@ -249,7 +249,7 @@ DREPHIP_EXPORT int drephip_last_screen_stats(drephip_ctx *ctx, int *used, uint64
 }
 
 DREPHIP_EXPORT int drephip_last_kernel_ms(drephip_ctx *ctx, int which, double *ms, int *launches) {
-    if (!ctx || which < 0 || which > 4 || !ms) { set_error("bad argument"); return DREPHIP_ERR_ARG; }
+    if (!ctx || which < 0 || which > 5 || !ms) { set_error("bad argument"); return DREPHIP_ERR_ARG; }
     *ms = ctx->kms[which];
     if (launches) *launches = ctx->kn[which];
     return DREPHIP_OK;
@@ -1471,6 +1471,57 @@ DREPHIP_EXPORT int drephip_dist_rect_sparse(drephip_ctx *ctx, const uint64_t *qh
     if (have) HIPC(hipMemcpyAsync(pairs, d_p, have * 16, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     return rc;
+}
+
+static int rect_top_args(uint32_t top) {
+    if (top < 1 || top > 64) { set_error("top must be in 1..64"); return DREPHIP_ERR_ARG; }
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_dist_rect_top_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash,
+                                                uint32_t Q, const uint64_t *d_rhashes, const uint32_t *d_rnhash,
+                                                uint32_t N, uint32_t q0, uint32_t q1, uint32_t top, uint32_t *d_hits,
+                                                uint32_t *d_count, void *stream) {
+    GUARD_CTX(ctx);
+    if (rect_null(d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N) || (Q && N && q0 < q1 && (!d_hits || !d_count))) {
+        set_error("null argument");
+        return DREPHIP_ERR_ARG;
+    }
+    int rc;
+    if ((rc = rect_top_args(top))) return rc;
+    timing_begin(ctx);
+    if ((rc = rect_top_impl(ctx, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1, top, d_hits, d_count,
+                            pick_stream(ctx, stream))))
+        return rc;
+    timing_collect(ctx);
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_dist_rect_top(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash, uint32_t Q,
+                                         const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint32_t q0,
+                                         uint32_t q1, uint32_t top, uint32_t *hits, uint32_t *count) {
+    GUARD_CTX(ctx);
+    if (rect_null(qhashes, qnhash, Q, rhashes, rnhash, N)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    int rc;
+    if ((rc = rect_top_args(top))) return rc;
+    if (q1 > Q) q1 = Q;
+    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
+    if (!hits || !count) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    if ((rc = check_rows(qhashes, qnhash, Q, ctx->s)) || (rc = check_rows(rhashes, rnhash, N, ctx->s))) return rc;
+    hipStream_t st = ctx->stream;
+    uint64_t *d_qh, *d_rh;
+    uint32_t *d_qn, *d_rn, *d_h, *d_n;
+    const uint64_t rows = q1 - q0;
+    if ((rc = rect_stage(ctx, qhashes, qnhash, Q, rhashes, rnhash, N, &d_qh, &d_qn, &d_rh, &d_rn))) return rc;
+    if ((rc = scratch(ctx, "rect_top_hits", rows * top * 16, (void **)&d_h))) return rc;
+    if ((rc = scratch(ctx, "rect_top_count", rows * 4, (void **)&d_n))) return rc;
+    timing_begin(ctx);
+    if ((rc = rect_top_impl(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, top, d_h, d_n, st))) return rc;
+    timing_collect(ctx);
+    HIPC(hipMemcpyAsync(hits, d_h, rows * top * 16, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(count, d_n, rows * 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return DREPHIP_OK;
 }
 
 DREPHIP_EXPORT int drephip_last_sparse_stats(drephip_ctx *ctx, uint32_t *blocks, uint64_t *direct, uint64_t *fallback,

@@ -170,8 +170,8 @@ struct drephip_ctx {
     // named grow-only device scratch buffers
     std::map<std::string, DevBuf> bufs;
     // per-kernel timing of the last call: {sum ms, launches}
-    double kms[5] = {0, 0, 0, 0, 0};
-    int kn[5] = {0, 0, 0, 0, 0};
+    double kms[6] = {0, 0, 0, 0, 0, 0};
+    int kn[6] = {0, 0, 0, 0, 0, 0};
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
     struct Span { int which; hipEvent_t a, b; };
@@ -325,6 +325,12 @@ int rect_device_impl(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t
 int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
                      const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0, uint32_t q1,
                      uint4 *d_pairs, uint64_t cap, uint64_t *n_pairs, hipStream_t st);
+// Per query row the `top` nearest references among those with common > 0, as
+// hits {r, common, denom, 0} (the contract of drephip_dist_rect_top_device):
+// query-row blocks into a scratch rectangle, k_rect_top after each.  Blocking.
+int rect_top_impl(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
+                  const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0, uint32_t q1,
+                  uint32_t top, uint32_t *d_hits, uint32_t *d_count, hipStream_t st);
 
 // Primary clustering (linkage.hip).
 int linkage_device_impl(drephip_ctx *ctx, double *d_D, uint32_t n, int method, double *Z_out, hipStream_t st);

@@ -952,6 +952,24 @@ def _rect_distance64(common: np.ndarray, denom: np.ndarray, k: int = MASH_K) -> 
     return out
 
 
+def _query_inputs(Qdb, data_folder, reference, max_dist, kwargs):
+    """What every query-against-reference call starts from: the reference
+    sketches (_read_reference's tuple), the queries' SketchSet -- sketched or
+    loaded from their cache in kwargs['query_folder'] at the reference's s --
+    and the devices.  Checks ingest and max_dist first."""
+    _check_ingest(kwargs)
+    if max_dist is not None and not (0 <= float(max_dist) < 1):
+        raise ValueError("max_dist must be in [0, 1): the record form lists only pairs that share a hash")
+    if reference is None:
+        reference = os.path.join(data_folder, 'MASH_files', 'ALL.msh')
+    ref = _read_reference(reference, kwargs)
+    qfolder = kwargs.get('query_folder', os.path.join(data_folder, 'MASH_query'))
+    skw = {k: v for k, v in kwargs.items() if k not in ('query_folder', 'max_dist')}
+    skw['MASH_sketch'] = ref[5]
+    sk = sketch_genomes(Qdb, qfolder, **skw)
+    return ref, sk, _devices(kwargs)
+
+
 def query_vs_MASH_rect(Qdb, data_folder, reference=None, **kwargs) -> RectMash:
     """The genomes of Qdb against a reference sketch file: the counts behind
     `mash dist <reference.msh> <query.msh>` (the two-file form of
@@ -966,18 +984,8 @@ def query_vs_MASH_rect(Qdb, data_folder, reference=None, **kwargs) -> RectMash:
     max_dist (default None: the dense Q x N form): the record form, only the
     pairs that share a hash.  gpu, gpus, processors and ingest as in
     all_vs_all_MASH."""
-    _check_ingest(kwargs)
     max_dist = kwargs.get('max_dist', None)
-    if max_dist is not None and not (0 <= float(max_dist) < 1):
-        raise ValueError("max_dist must be in [0, 1): the record form lists only pairs that share a hash")
-    if reference is None:
-        reference = os.path.join(data_folder, 'MASH_files', 'ALL.msh')
-    rnames, rlocs, rh, rn, rlen, s = _read_reference(reference, kwargs)
-    qfolder = kwargs.get('query_folder', os.path.join(data_folder, 'MASH_query'))
-    skw = {k: v for k, v in kwargs.items() if k not in ('query_folder', 'max_dist')}
-    skw['MASH_sketch'] = s
-    sk = sketch_genomes(Qdb, qfolder, **skw)
-    devs = _devices(kwargs)
+    (rnames, rlocs, rh, rn, rlen, s), sk, devs = _query_inputs(Qdb, data_folder, reference, max_dist, kwargs)
     with _Stage('rect_s'):
         if max_dist is None:
             common, denom = rect_allpairs(sk.hashes, sk.nhash, rh, rn, s, devs)
@@ -1023,16 +1031,18 @@ def mdb_from_rect(rm: RectMash, k: int = MASH_K, max_dist: Optional[float] = Non
     lut32, lut_off = float32_tables(dens, rm.s, k)
     dist = lut32[lut_off[d.astype(np.int64)].astype(np.int64) + c.astype(np.int64)].astype(np.float32) if len(d) \
         else np.zeros(0, np.float32)
-
-    def cat(names, idx):
-        cats = sorted(set(names))
-        dtype = pd.CategoricalDtype(cats, ordered=True)
-        code_t = pd.Categorical([], dtype=dtype).codes.dtype
-        pos = {n: x for x, n in enumerate(cats)}
-        codes = np.array([pos[n] for n in names], dtype=code_t)
-        return pd.Categorical.from_codes(codes[idx] if len(codes) else np.zeros(0, code_t), dtype=dtype, validate=False)
-    return pd.DataFrame({'genome1': cat(rm.rnames, r), 'genome2': cat(rm.qnames, q),
+    return pd.DataFrame({'genome1': _name_categorical(rm.rnames, r), 'genome2': _name_categorical(rm.qnames, q),
                          'dist': dist, 'similarity': np.float32(1) - dist}, copy=False)
+
+
+def _name_categorical(names, idx):
+    """names[idx] as an ordered categorical over the sorted names."""
+    cats = sorted(set(names))
+    dtype = pd.CategoricalDtype(cats, ordered=True)
+    code_t = pd.Categorical([], dtype=dtype).codes.dtype
+    pos = {n: x for x, n in enumerate(cats)}
+    codes = np.array([pos[n] for n in names], dtype=code_t)
+    return pd.Categorical.from_codes(codes[idx] if len(codes) else np.zeros(0, code_t), dtype=dtype, validate=False)
 
 
 def query_vs_MASH(Qdb, data_folder, reference=None, **kwargs):
@@ -1088,3 +1098,144 @@ def union_condensed(cm_ref: CondensedMash, rm: RectMash, cm_query: CondensedMash
     return CondensedMash(list(cm_ref.names) + list(cm_query.names), list(cm_ref.locations) + list(cm_query.locations),
                          out[0], out[1], np.concatenate([np.asarray(cm_ref.nhash), np.asarray(cm_query.nhash)]),
                          np.concatenate([np.asarray(cm_ref.length), np.asarray(cm_query.length)]), cm_ref.s)
+
+
+# ------------------------------------------------- best hits and placement
+# What a caller of `mash dist <reference.msh> <queries>` usually keeps: each
+# query's nearest references, and from them the primary cluster a new genome
+# falls into.  The selection runs on the GPU (drephip_dist_rect_top), so neither
+# the Q x N rectangle nor the record list comes to the host.
+def rect_top_hits(qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray, s: int,
+                  top: int, devices: Sequence[int] = (0,)):
+    """(ref int64 [Q, top], common uint16 [Q, top], denom uint16 [Q, top],
+    count uint32 [Q]): per query the `top` (1..64) nearest references among
+    those that share a hash with it, nearest first, ties by the smaller
+    reference row (libdrephip drephip_dist_rect_top); unused slots hold ref -1.
+    Query rows are split over the devices as rect_allpairs splits them."""
+    qhashes, qnhash, rhashes, rnhash = _lib.rect_arrays(qhashes, qnhash, rhashes, rnhash, s)
+    top = int(top)
+    if not 1 <= top <= 64:
+        raise ValueError("top must be in 1..64")
+    Q, N = len(qnhash), len(rnhash)
+    ref = np.full((Q, top), -1, dtype=np.int64)
+    common = np.zeros((Q, top), dtype=np.uint16)
+    denom = np.zeros((Q, top), dtype=np.uint16)
+    count = np.zeros(Q, dtype=np.uint32)
+    parts = _query_ranges(Q, len(devices))
+
+    def run(k, dev):
+        a, b = parts[k]
+        if b <= a:
+            return
+        with _lib.Context(device=dev, k=MASH_K, s=s, seed=MASH_SEED) as ctx:
+            ref[a:b], common[a:b], denom[a:b], count[a:b] = ctx.dist_rect_top(qhashes, qnhash, rhashes, rnhash,
+                                                                               top, a, b)
+    if Q and N:
+        _on_devices(list(devices), run)
+    return ref, common, denom, count
+
+
+def best_hits_frame(qnames: Sequence[str], rnames: Sequence[str], ref: np.ndarray, common: np.ndarray,
+                    denom: np.ndarray, count: np.ndarray, s: int, k: int = MASH_K,
+                    max_dist: Optional[float] = None) -> pd.DataFrame:
+    """rect_top_hits' arrays as the table query_best_hits returns (its
+    docstring).  Pure pandas/numpy plus the distance tables."""
+    ref, count = np.asarray(ref, dtype=np.int64), np.asarray(count, dtype=np.int64)
+    top = ref.shape[1] if ref.ndim == 2 else 0
+    listed = np.arange(top, dtype=np.int64)[None, :] < count[:, None]
+    q, rank = np.nonzero(listed)                                   # query-outer, rank-inner
+    r = ref[q, rank]
+    c = np.asarray(common, dtype=np.uint16)[q, rank]
+    d = np.asarray(denom, dtype=np.uint16)[q, rank]
+    if max_dist is not None:
+        keep = _rect_distance64(c, d, k) <= float(max_dist)
+        q, rank, r, c, d = q[keep], rank[keep], r[keep], c[keep], d[keep]
+    dens = np.unique(d) if len(d) else np.array([s])
+    lut32, lut_off = float32_tables(dens, s, k)
+    dist = lut32[lut_off[d.astype(np.int64)].astype(np.int64) + c.astype(np.int64)].astype(np.float32) if len(d) \
+        else np.zeros(0, np.float32)
+    return pd.DataFrame({'genome1': _name_categorical(rnames, r), 'genome2': _name_categorical(qnames, q),
+                         'rank': rank.astype(np.int32), 'dist': dist, 'similarity': np.float32(1) - dist,
+                         'common': c, 'denom': d}, copy=False)
+
+
+def query_best_hits(Qdb, data_folder, reference=None, top=1, max_dist=None, **kwargs) -> pd.DataFrame:
+    """Each genome of Qdb against a reference sketch file: its `top` (1..64)
+    nearest references, selected on the GPU.
+
+    Args and keyword args as query_vs_MASH_rect (reference, query_folder, gpu,
+    gpus, processors, ingest).  Only references that share a hash with the
+    query are ever listed (Mash distance < 1).  max_dist keeps the rows whose
+    float64 Mash distance (drephip_distance_lut) is <= max_dist, the rule of
+    mdb_from_rect.
+
+    Returns:
+        DataFrame [genome1 (reference), genome2 (query), rank (0-based, nearest
+        first; ties by the reference's row in the .msh file), dist, similarity,
+        common, denom], rows query-outer, rank-inner.  dist is float32 through
+        the %g / read_csv route (float32_tables), so a row's dist and
+        similarity are bit for bit those of the same pair in query_vs_MASH.
+    """
+    (rnames, _, rh, rn, _, s), sk, devs = _query_inputs(Qdb, data_folder, reference, max_dist, kwargs)
+    with _Stage('rect_top_s'):
+        ref, common, denom, count = rect_top_hits(sk.hashes, sk.nhash, rh, rn, s, top, devs)
+    with _Stage('mdb_s'):
+        return best_hits_frame(sk.names, rnames, ref, common, denom, count, s, max_dist=max_dist)
+
+
+def place_queries(hits: pd.DataFrame, Cdb: pd.DataFrame, P_ani: float = 0.9) -> pd.DataFrame:
+    """Which existing primary cluster each query of a query_best_hits table
+    falls into, by its listed hits.
+
+    hits: the frame of query_best_hits; Cdb: [genome, primary_cluster] of the
+    references (clusters numbered from 1, as cluster_mash_database numbers
+    them).  A hit is within the threshold when its float64 Mash distance
+    (drephip_distance_lut of its common / denom) is <= 1 - P_ani.
+
+    Returns one row per query: the queries with rows in hits in the order of
+    their first rows, then the queries without any hit (they have no row in
+    hits, but query_best_hits keeps every query's name among genome2's
+    categories):
+        genome, nearest (the rank-0 reference, None without one), dist (its
+        float32 dist, NaN without one), primary_cluster (that of the rank-0 hit
+        when it is within the threshold, else 0), n_clusters (the distinct
+        primary clusters among the listed hits within the threshold; use it
+        with top > 1: a value above 1 means the genome bridges clusters).
+    A hit whose reference is missing from Cdb raises ValueError.
+
+    What this is: for clusterAlg='single' it is exactly the cluster the query
+    gets when the references and the query are re-clustered, provided every
+    hit within the threshold is listed (count < top, or the last listed hit is
+    already outside) and they all fall in one cluster (n_clusters <= 1).  What
+    it is not: for n_clusters > 1 single linkage would merge those clusters,
+    which a placement cannot express; for average, complete and the other
+    methods this is the nearest-reference rule, not a re-clustering.
+    union_condensed plus cluster_mash_condensed remains the exact route."""
+    for col in ('genome1', 'genome2', 'rank', 'dist', 'common', 'denom'):
+        if col not in hits.columns:
+            raise ValueError("hits must be a query_best_hits table: no column %r" % col)
+    cluster = dict(zip(Cdb['genome'].astype(str), Cdb['primary_cluster'].astype(np.int64)))
+    g1 = hits['genome1'].astype(str).to_numpy()
+    g2 = hits['genome2'].astype(str).to_numpy()
+    missing = sorted(set(g1) - set(cluster))
+    if missing:
+        raise ValueError("hits name references that Cdb does not hold: %s" % ", ".join(missing[:5]))
+    within = _rect_distance64(hits['common'].to_numpy(), hits['denom'].to_numpy()) <= 1.0 - float(P_ani)
+    cl = np.array([cluster[n] for n in g1], dtype=np.int64)
+    q, order = pd.factorize(g2)                                    # queries in the order of their first rows
+    order = list(order)
+    if isinstance(hits['genome2'].dtype, pd.CategoricalDtype):
+        seen = set(order)
+        order += [n for n in hits['genome2'].cat.categories if n not in seen]
+    nq = len(order)
+    nearest = np.full(nq, None, dtype=object)
+    dist = np.full(nq, np.nan, dtype=np.float32)
+    primary = np.zeros(nq, dtype=np.int64)
+    first = hits['rank'].to_numpy() == 0
+    nearest[q[first]] = g1[first]
+    dist[q[first]] = hits['dist'].to_numpy()[first]
+    primary[q[first & within]] = cl[first & within]
+    pairs = np.unique(np.stack([q[within], cl[within]], axis=1), axis=0) if within.any() else np.zeros((0, 2), np.int64)
+    n_clusters = np.bincount(pairs[:, 0], minlength=nq).astype(np.int64)
+    return pd.DataFrame({'genome': order, 'nearest': nearest, 'dist': dist, 'primary_cluster': primary,
+                         'n_clusters': n_clusters})

@@ -524,6 +524,37 @@ int drephip_dist_rect_sparse_device(drephip_ctx *ctx, const uint64_t *d_qhashes,
 int drephip_dist_rect_sparse(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash, uint32_t Q,
                              const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint32_t q0, uint32_t q1,
                              uint32_t *pairs /* cap x 4 */, uint64_t cap, uint64_t *n_pairs);
+/* Best hits of `mash dist <reference.msh> <query.msh>`: for each query row q
+ * of [q0, min(q1, Q)) the `top` (1..64, else DREPHIP_ERR_ARG) references
+ * nearest to it by Mash distance among those that share a hash with it
+ * (common > 0; the 0 / 0 pair of two empty sketches is never listed, as in the
+ * record form).  Hit t of row q is 4 uint32 {r, common, denom, 0} at
+ * ((q - q0) * top + t) * 4, common and denom exactly drephip_dist_rect's cell
+ * (q, r); d_count[q - q0] = min(top, references with common > 0); the slots at
+ * or past it hold {0xFFFFFFFF, 0, 0, 0}; nothing else is written.  Order:
+ * larger common / denom first, compared as exact rationals (for common > 0
+ * the Mash distance falls strictly with the ratio and never reaches its clamp
+ * at 1, denom <= 32767), equal ratios by smaller r: a total order, so the
+ * result is deterministic, and a query that is also a reference lists itself
+ * first with common == denom.  Q == 0, N == 0 or q0 >= q1: DREPHIP_OK,
+ * nothing written; null pointers: DREPHIP_ERR_ARG.  No Q x N buffer: the
+ * query rows are walked in blocks of at most 2^28 cells (at least one row;
+ * DREPHIP_RECT_TOP_BLOCK_ROWS sets fewer rows, for tests), each block's counts
+ * by the rectangle's kernel (as drephip_dist_rect_device picks it;
+ * DREPHIP_AP_BAND: DREPHIP_ERR_UNSUPPORTED) into a scratch rectangle of the
+ * context (common + denom, at most 1 GB), then k_rect_top selects per row.
+ * Blocking, on the caller's stream; a pending drephip_allpairs_device_async
+ * is waited for first.  drephip_last_kernel_ms `which` 5 is the selection
+ * kernel summed over the blocks, 2 / 3 the counts kernel and its table build. */
+int drephip_dist_rect_top_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
+                                 const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0,
+                                 uint32_t q1, uint32_t top, uint32_t *d_hits /* (q1 - q0) x top x 4 */,
+                                 uint32_t *d_count /* q1 - q0 */, void *stream);
+/* The host form of the best hits; both matrices staged and checked as
+ * drephip_dist_rect does. */
+int drephip_dist_rect_top(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash, uint32_t Q,
+                          const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint32_t q0, uint32_t q1,
+                          uint32_t top, uint32_t *hits /* (q1 - q0) x top x 4 */, uint32_t *count /* q1 - q0 */);
 
 /* ---------------------------------------------------------- primary clustering
  * Replaces: scipy.cluster.hierarchy.linkage(squareform(dist), method) in
@@ -658,7 +689,8 @@ int drephip_set_timing(drephip_ctx *ctx, int kernels);
 /* Per-launch timing of the last sketch/allpairs call on this context
  * (milliseconds, from HIP events on the launch stream): which = 0 sketch hash
  * kernel, 1 sketch finalize kernel, 2 allpairs kernel, 3 table build kernel,
- * 4 the shared-hash screen (grouping + lists, including its host round trips).
+ * 4 the shared-hash screen (grouping + lists, including its host round trips),
+ * 5 the best-hits selection kernel (drephip_dist_rect_top*).
  * Returns the count of launches summed into *ms. */
 int drephip_last_kernel_ms(drephip_ctx *ctx, int which, double *ms, int *launches);
 
