@@ -1409,6 +1409,7 @@ struct ItemPlan {
     std::vector<ItemGroup> groups;
     XcdStarts xs{};
     uint64_t slots = 0;                          // kXcds x the longest list
+    uint64_t gmax = 0;                           // the largest group (plan_rect_items; DREPHIP_DEBUG)
 };
 
 static ItemPlan plan_items(uint32_t row0, uint32_t row1, uint32_t N, uint32_t R, uint32_t C) {
@@ -2123,6 +2124,7 @@ static ItemPlan plan_rect_items(uint32_t q0, uint32_t q1, uint32_t Nc, uint32_t 
     }
     p.xs.v[kXcds] = (uint32_t)p.groups.size();
     p.slots = lmax * kXcds;
+    p.gmax = gmax;
     return p;
 }
 
@@ -2184,10 +2186,17 @@ static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_
     // the plan is not cached: its key (Q, q0, q1, N, R, C) is not the
     // triangle's, and planning is a few thousand groups on the host
     uint64_t ni64;
-    if ((rc = expand_items<true>(ctx, plan_rect_items(q0, q1, N, R, C), groups, "rect_items", R, C, st,
-                                 (void **)&d_items, &ni64)))
+    ItemPlan plan = plan_rect_items(q0, q1, N, R, C);
+    const uint64_t gmax = plan.gmax;
+    if ((rc = expand_items<true>(ctx, std::move(plan), groups, "rect_items", R, C, st, (void **)&d_items, &ni64)))
         return rc;
     const uint32_t ni = (uint32_t)ni64;
+    if (getenv("DREPHIP_DEBUG")) {                  // the geometry this call runs at (the tests read it)
+        const uint64_t per = max_blocks(kApWG);     // items per k_allpairs_q dispatch (launch_rect_q)
+        fprintf(stderr, "[drephip] rect plan: R %u C %u items %llu slots %llu gmax %llu pieces %u\n", R, C,
+                (unsigned long long)nitems_for(C), (unsigned long long)ni64, (unsigned long long)gmax,
+                (uint32_t)((ni64 + per - 1) / per));
+    }
     const size_t lds = (size_t)stride * 4;
     const uint32_t nch = (s + 63) / 64;
     const bool two = lds <= 80 * 1024;              // two workgroups per CU when the LDS allows
@@ -2266,6 +2275,16 @@ int rect_device_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_q
 
 constexpr uint64_t kRectBlockPairs = 1ull << 28;    // cells per scratch rectangle of the merge route's records
 
+// Query rows per scratch rectangle: at most kRectBlockPairs cells, at least
+// one row.  The environment variable `knob` (tests only) lowers it: a value
+// <= 0 is ignored.
+static uint32_t rect_block_rows(uint32_t N, const char *knob) {
+    uint32_t rows = (uint32_t)std::max<uint64_t>(1, kRectBlockPairs / N);
+    if (const char *e = getenv(knob))
+        if (atoi(e) > 0) rows = std::min<uint32_t>(rows, (uint32_t)atoi(e));
+    return rows;
+}
+
 int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
                      const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint4 *d_pairs, uint64_t cap,
                      uint64_t *n_pairs, hipStream_t st) {
@@ -2291,7 +2310,7 @@ int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_q
         if ((rc = rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, R, nullptr, nullptr, &out, groups, st))) return rc;
     } else {
         // query-row blocks of at most kRectBlockPairs cells (at least one row)
-        const uint32_t rows = (uint32_t)std::max<uint64_t>(1, kRectBlockPairs / N);
+        const uint32_t rows = rect_block_rows(N, "DREPHIP_RECT_BLOCK_ROWS");
         const uint64_t bcells = (uint64_t)std::min<uint32_t>(rows, q1 - q0) * N;
         uint16_t *d_c, *d_d;
         if ((rc = scratch(ctx, "rect_blk_common", bcells * 2, (void **)&d_c))) return rc;
@@ -2335,10 +2354,8 @@ int rect_top_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, 
     if ((rc = rect_path(ctx, false, &R, &path))) return rc;
     ctx->last_screen = ScreenResult{};
     // query-row blocks of at most kRectBlockPairs cells (at least one row), as
-    // the record form's merge route; DREPHIP_RECT_TOP_BLOCK_ROWS: fewer (tests)
-    uint32_t rows = (uint32_t)std::max<uint64_t>(1, kRectBlockPairs / N);
-    if (const char *e = getenv("DREPHIP_RECT_TOP_BLOCK_ROWS"))
-        if (atoi(e) > 0) rows = std::min<uint32_t>(rows, (uint32_t)atoi(e));
+    // the record form's merge route
+    const uint32_t rows = rect_block_rows(N, "DREPHIP_RECT_TOP_BLOCK_ROWS");
     const uint64_t bcells = (uint64_t)std::min<uint32_t>(rows, q1 - q0) * N;
     uint16_t *d_c, *d_d;
     // 16 bytes more: k_rect_top reads whole 16-byte words up to the last row's end

@@ -513,8 +513,13 @@ int drephip_dist_rect(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t 
  * only counts; with too few slots only [0, cap) is written, the call returns
  * DREPHIP_ERR_NOMEM and *n_pairs is the size needed.  s <= 2048: the RECT
  * kernel stages and appends the records itself, no rectangle is written.
- * Above, and for DREPHIP_AP_MERGE: query-row blocks of at most 2^28 pairs,
- * each merged into a scratch rectangle of the context and compacted. */
+ * Above, and for DREPHIP_AP_MERGE: query-row blocks of at most 2^28 pairs
+ * (at least one row; DREPHIP_RECT_BLOCK_ROWS sets fewer rows, for tests),
+ * each merged into a scratch rectangle of the context and compacted.  With
+ * DREPHIP_DEBUG set, the RECT kernel's plan is printed to stderr, one line
+ * per call: "[drephip] rect plan: R .. C .. items .. slots .. gmax .. pieces
+ * .." (row tile, column tile, (row tile, column tile) pairs, item slots with
+ * the idle ones, largest group, kernel dispatches). */
 int drephip_dist_rect_sparse_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
                                     const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0,
                                     uint32_t q1, uint32_t *d_pairs /* cap x 4 */, uint64_t cap, uint64_t *n_pairs,
