@@ -1818,6 +1818,26 @@ int allpairs_device_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
     // Its group table lives in the context until the next plan replaces it (the
     // queued H2D copy may still be reading it when a deferred call returns).
     const uint64_t key[5] = {N, row0, row1, R, C};
+    if (getenv("DREPHIP_DEBUG")) {                  // the geometry this call runs at (the tests read it)
+        // the branches below, restated: the screened items, the cached list, or a new plan's slots;
+        // cmax: the most columns of one item (the screened items are read back)
+        const bool cached = !scr.use && ctx->ap_items_gen == ctx->alloc_gen && !memcmp(ctx->ap_items_key, key, sizeof(key));
+        uint64_t items = nitems_for(C), slots = cached ? ctx->ap_items_n : 0, cmax = std::min(C, N);
+        if (scr.use) {
+            std::vector<uint4> h(scr.nitems);
+            HIPC(hipStreamSynchronize(st));
+            if (scr.nitems) HIPC(hipMemcpy(h.data(), scr.items, scr.nitems * sizeof(uint4), hipMemcpyDeviceToHost));
+            items = cmax = 0;
+            slots = scr.nitems;
+            for (const uint4 &it : h)
+                if (it.x != kIdleItem) { items++; cmax = std::max<uint64_t>(cmax, it.z); }
+        } else if (!cached) {
+            slots = plan_items(row0, row1, N, R, C).slots;
+        }
+        fprintf(stderr, "[drephip] ap plan: R %u C %u items %llu slots %llu list %d cmask %d cached %d cmax %llu\n", R, C,
+                (unsigned long long)items, (unsigned long long)slots, (int)scr.use,
+                (int)(scr.cmask != nullptr && !scr.use), (int)cached, (unsigned long long)cmax);
+    }
     if (scr.use) {
         // the screened items (the screen has written every other pair)
         d_items = (uint4 *)scr.items;

@@ -251,6 +251,23 @@ def cond_index(i, j, N):
     return i * N - i * (i + 1) // 2 + (j - i - 1)
 
 
+def permuted_condensed(common, denom, N, perm):
+    """The condensed (common, denom) of the set (H[perm], NH[perm]) from those
+    of (H, NH), through the symmetric N x N square (both counts are symmetric
+    in the pair): a second data set per shape without another reference run."""
+    perm = np.asarray(perm, dtype=np.int64)
+    assert np.array_equal(np.sort(perm), np.arange(N))
+    ii, jj = np.triu_indices(N, 1)
+    out = []
+    for a in (common, denom):
+        assert len(a) == N * (N - 1) // 2
+        M = np.zeros((N, N), dtype=a.dtype)
+        M[ii, jj] = a
+        M[jj, ii] = a
+        out.append(np.ascontiguousarray(M[perm[:, None], perm[None, :]][ii, jj]))
+    return out[0], out[1]
+
+
 # ---------------------------------------------------------------- sketch references
 _COMP = bytes.maketrans(b"ACGT", b"TGCA")
 _ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)

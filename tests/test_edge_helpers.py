@@ -22,6 +22,24 @@ def test_ref_allpairs_equals_oracle_on_geometry_sketches(s, N):
     assert (oc > 0).mean() > 0.5
 
 
+@pytest.mark.parametrize("how", ["reversed", "random"])
+def test_permuted_condensed_equals_reference_of_the_permuted_set(how):
+    """The counts of a row permutation cut out of the original condensed
+    arrays equal ref_allpairs of the permuted set (the counts are not uniform:
+    a permutation that moved nothing, or the wrong way, would show)."""
+    s, N = 64, 45
+    H, NH = ec.geometry_sketches(N, s, seed=31)
+    rc, rd = ec.ref_allpairs(H, NH, s)
+    perm = np.arange(N)[::-1] if how == "reversed" else np.random.default_rng(5).permutation(N)
+    pc, pd = ec.permuted_condensed(rc, rd, N, perm)
+    ec_, ed_ = ec.ref_allpairs(H[perm], NH[perm], s)
+    assert pc.dtype == np.uint16 and pd.dtype == np.uint16
+    assert np.array_equal(pc, ec_) and np.array_equal(pd, ed_)
+    assert not np.array_equal(pc, rc) and not np.array_equal(pd, rd)
+    ic, id_ = ec.permuted_condensed(rc, rd, N, np.arange(N))
+    assert np.array_equal(ic, rc) and np.array_equal(id_, rd)
+
+
 def test_ref_pair_tiny_sets():
     """The reference on sets small enough to check by eye."""
     u = lambda *v: np.array(v, dtype=np.uint64)
