@@ -114,6 +114,8 @@ SIGNATURES = {
     "drephip_write_mash_table": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, vp, vp, C.c_uint32,
                                            vp, vp, u16p, f64p, C.c_int]),
     "drephip_set_allpairs_path": (C.c_int, [vp, C.c_int, C.c_uint32]),
+    "drephip_set_rect_band": (C.c_int, [vp, C.c_int, C.c_uint32]),
+    "drephip_last_rect_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "drephip_linkage": (C.c_int, [vp, f64p, C.c_uint32, C.c_int, f64p]),
     "drephip_linkage_counts_device": (C.c_int, [vp, vp, vp, C.c_uint32, u32p, f64p, C.c_uint32,
                                                 np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS"),
@@ -491,6 +493,23 @@ class Context:
 
     def set_allpairs_path(self, path: int, band_cap: int = 1024) -> None:
         check(lib().drephip_set_allpairs_path(self._h, path, band_cap), "drephip_set_allpairs_path")
+
+    # the rectangle's band kernel (include/drephip.h DREPHIP_RECT_BAND_*)
+    RECT_BAND_AUTO, RECT_BAND_OFF, RECT_BAND_FORCE = 0, 1, 2
+
+    def set_rect_band(self, mode: int, band_cap: int = 768) -> None:
+        """Which kernel the query-against-reference calls take above the
+        whole-row tables (auto: the band kernel; off: the literal merge;
+        force: the band kernel at every s) and its elements per row per band."""
+        check(lib().drephip_set_rect_band(self._h, int(mode), int(band_cap)), "drephip_set_rect_band")
+
+    def last_rect_info(self) -> Tuple[int, int]:
+        """(kernel, fallback) of the last rectangle call: AP_TABLE / AP_BAND /
+        AP_MERGE, and 1 when rows were rerun by the merge kernel after an
+        unbuildable band table."""
+        k, f = C.c_int(0), C.c_int(0)
+        check(lib().drephip_last_rect_info(self._h, C.byref(k), C.byref(f)), "drephip_last_rect_info")
+        return k.value, f.value
 
     LINK_METHODS = LINK_METHODS
     # linkage path (include/drephip.h DREPHIP_LINK_PATH_*)

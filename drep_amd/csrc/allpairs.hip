@@ -1019,7 +1019,8 @@ __device__ __forceinline__ uint64_t tail_mask(uint32_t j0, uint32_t s) {     // 
 // words are read one chunk ahead of the tests.  After the band a column goes
 // on the next band's list (next, *nnext) unless its union-rank end has passed
 // for every row with the next band's row positions pn.
-template <int R, uint32_t NW, int BB, int CAP, bool FAST, bool RETRY, bool LIST>
+// RECT: `hashes` is the reference matrix and every row meets every column.
+template <int R, uint32_t NW, int BB, int CAP, bool FAST, bool RETRY, bool LIST, bool RECT = false>
 __device__ __forceinline__ void band_columns(const uint64_t *__restrict__ hashes, uint32_t s, const uint32_t *T,
                                              const uint32_t *V, uint32_t *cur, uint16_t *pcnt, uint16_t *pm,
                                              const uint8_t *live, uint32_t nlive, uint8_t *next, uint32_t *nnext,
@@ -1056,7 +1057,7 @@ __device__ __forceinline__ void band_columns(const uint64_t *__restrict__ hashes
         if (li + NW < nlive) { cnx = rfl(live[li + NW]); load_first(cnx); }
         uint32_t actmask = 0;
 #pragma unroll
-        for (int r = 0; r < R; r++) actmask |= (uint32_t)((uint32_t)r < nrows && i0 + r < c) << r;
+        for (int r = 0; r < R; r++) actmask |= (uint32_t)((uint32_t)r < nrows && (RECT || i0 + r < c)) << r;
         uint32_t mrun[R], cnt[R];
 #pragma unroll
         for (int r = 0; r < R; r++) { mrun[r] = rfl(pm[r * kBandCols + ci]); cnt[r] = 0; }   // scalar counters
@@ -1146,16 +1147,25 @@ enum : uint32_t { kBsDone = 1u };
 // (litems) over the column list clist; otherwise {i0, c0} over kBandCols
 // consecutive columns.  ROUNDS: one value round per launch (above); bstate
 // holds this launch's items' states, ends the rounds' upper bounds.
-template <int R, int BB, int CAP, int WG, int MINW, bool LIST = false, bool ROUNDS = false>
+// RECT (drephip_dist_rect_device, s > 2048): the rows [.., row1) are queries
+// (hashes, nhash, N = Q), the columns the reference matrix rc; no diagonal --
+// every column of the item is live and every cell is written, pair (q, r) at
+// q * rc.n + r - seg0 (seg0 = q0 * rc.n).  Neither LIST nor ROUNDS.
+template <int R, int BB, int CAP, int WG, int MINW, bool LIST = false, bool ROUNDS = false, bool RECT = false>
 __global__ __launch_bounds__(WG, MINW) void k_allpairs_band(
     const uint64_t *__restrict__ hashes, const uint32_t *__restrict__ nhash, uint32_t s, uint32_t N,
     uint32_t row1, uint32_t cap, const uint2 *__restrict__ items, uint16_t *__restrict__ common,
     uint16_t *__restrict__ denom, uint64_t seg0, uint32_t *__restrict__ nfail, uint64_t *__restrict__ prof,
     const uint4 *__restrict__ litems, const uint32_t *__restrict__ clist, uint32_t *__restrict__ bstate,
-    const uint64_t *__restrict__ ends, uint32_t round) {
+    const uint64_t *__restrict__ ends, uint32_t round, RectCols rc) {
     constexpr uint32_t H = 1u << BB, hm = H - 1, TS = 2 * H;
     constexpr uint32_t NW = WG / 64;
     static_assert(CAP < H, "band positions stay below the empty word's position hm");
+    static_assert(!(RECT && (LIST || ROUNDS)), "the rectangle has neither a screen nor value rounds");
+    // the column side: the matrix itself, or (RECT) the reference matrix
+    const uint64_t *__restrict__ chashes = RECT ? rc.hashes : hashes;
+    const uint32_t *__restrict__ cnhash = RECT ? rc.nhash : nhash;
+    const uint32_t Nc = RECT ? rc.n : N;
     extern __shared__ __align__(16) uint32_t lds[];    // 16-B aligned: slot words are read with ds_read_b128
     uint32_t *T = lds;                                               // [TS][R] interleaved slot words
     uint32_t *V = T + R * TS;                                        // [R][CAP] high words
@@ -1176,7 +1186,7 @@ __global__ __launch_bounds__(WG, MINW) void k_allpairs_band(
     if (ROUNDS && round > 0 && (gst[BW + R + 3] & kBsDone)) return;          // finished in an earlier round
     const uint32_t nrows = min((uint32_t)R, row1 - i0);
     const uint32_t *cl = LIST ? clist + litems[blockIdx.x].y : nullptr;
-    const uint32_t ncols = LIST ? litems[blockIdx.x].z : min(c0 + kBandCols, N) - c0;
+    const uint32_t ncols = LIST ? litems[blockIdx.x].z : min(c0 + kBandCols, Nc) - c0;
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t wave = rfl(tid >> 6);          // wave-uniform for the compiler: scalar column loop
 
@@ -1211,9 +1221,9 @@ __global__ __launch_bounds__(WG, MINW) void k_allpairs_band(
         if (tid == 0) { s_abort = 0; s_nlive[0] = 0; s_nlive[1] = 0; s_lo = 0; }
         __syncthreads();
         // the first band's list: every column right of the tile's first row
-        // (columns left of every row have no pair in the item)
+        // (columns left of every row have no pair in the item); RECT: every column
         for (uint32_t k = tid; k < ncols; k += WG)
-            if (i0 < (LIST ? cl[k] : c0 + k)) lists[atomicAdd(&s_nlive[0], 1u)] = (uint8_t)k;
+            if (RECT || i0 < (LIST ? cl[k] : c0 + k)) lists[atomicAdd(&s_nlive[0], 1u)] = (uint8_t)k;
     }
 
     for (uint32_t band = band0;; band++) {
@@ -1315,13 +1325,13 @@ __global__ __launch_bounds__(WG, MINW) void k_allpairs_band(
         uint8_t *next = lists + (lb ^ 1u) * kBandCols;
         const uint32_t nlive = s_nlive[lb];
         if (fam == 0 && !s_twin)
-            band_columns<R, NW, BB, CAP, true, false, LIST>(hashes, s, T, V, cur, pcnt, pm, live, nlive, next, &s_nlive[lb ^ 1u],
+            band_columns<R, NW, BB, CAP, true, false, LIST, RECT>(chashes, s, T, V, cur, pcnt, pm, live, nlive, next, &s_nlive[lb ^ 1u],
                                                       c0, cl, i0, nrows, wave, hi, fam, pr, pn);
         else if (fam == 0)
-            band_columns<R, NW, BB, CAP, true, true, LIST>(hashes, s, T, V, cur, pcnt, pm, live, nlive, next, &s_nlive[lb ^ 1u],
+            band_columns<R, NW, BB, CAP, true, true, LIST, RECT>(chashes, s, T, V, cur, pcnt, pm, live, nlive, next, &s_nlive[lb ^ 1u],
                                                      c0, cl, i0, nrows, wave, hi, fam, pr, pn);
         else
-            band_columns<R, NW, BB, CAP, false, true, LIST>(hashes, s, T, V, cur, pcnt, pm, live, nlive, next, &s_nlive[lb ^ 1u],
+            band_columns<R, NW, BB, CAP, false, true, LIST, RECT>(chashes, s, T, V, cur, pcnt, pm, live, nlive, next, &s_nlive[lb ^ 1u],
                                                       c0, cl, i0, nrows, wave, hi, fam, pr, pn);
         __syncthreads();
         if (tid < (uint32_t)R) s_p[tid] += s_q[tid];
@@ -1340,7 +1350,7 @@ __global__ __launch_bounds__(WG, MINW) void k_allpairs_band(
         // the screened columns: one pair per (row, list entry) right of the row
         for (uint32_t t = tid; t < nrows * ncols; t += WG) {
             const uint32_t r = t / ncols, ci = t - r * ncols, i = i0 + r, c = cl[ci];
-            if (c <= i) continue;
+            if (!RECT && c <= i) continue;
             uint32_t nl = 0;
 #pragma unroll
             for (int rr = 0; rr < R; rr++) if ((uint32_t)rr == r) nl = nA[rr];
@@ -1361,17 +1371,17 @@ __global__ __launch_bounds__(WG, MINW) void k_allpairs_band(
     const uint32_t cend = c0 + ncols;
     for (uint32_t r = 0; r < nrows; r++) {
         const uint32_t i = i0 + r;
-        const uint32_t cs = max(c0, i + 1);
+        const uint32_t cs = RECT ? c0 : max(c0, i + 1);
         if (cs >= cend) continue;
         uint32_t nl = 0;
 #pragma unroll
         for (int rr = 0; rr < R; rr++) if ((uint32_t)rr == r) nl = nA[rr];
-        const uint64_t base = cond_index(i, cs, N) - seg0;
+        const uint64_t base = (RECT ? (uint64_t)i * Nc + cs : cond_index(i, cs, N)) - seg0;
         for (uint32_t t = tid; t < cend - cs; t += WG) {
             const uint32_t ci = cs - c0 + t;
             common[base + t] = (uint16_t)pcnt[r * kBandCols + ci];
             if (denom) {
-                const uint32_t nB = nhash[cs + t];
+                const uint32_t nB = cnhash[cs + t];
                 uint32_t dd = s;
                 if (any_partial_row || nB < s) {
                     const uint32_t u = nl + nB - pm[r * kBandCols + ci];
@@ -1617,7 +1627,7 @@ static int launch_band_cfg(drephip_ctx *ctx, const uint64_t *d_hashes, const uin
                                    st, d_hashes, d_nhash, ctx->s, N, row1, cap, scr ? nullptr : d_items + i0, d_common,
                                    d_denom, seg0, d_nfail, d_prof, scr ? scr->items + i0 : nullptr,
                                    scr ? scr->clist : nullptr, rounds ? d_state + (i0 - b0) * band_state_words<R>() : nullptr,
-                                   d_ends, k);
+                                   d_ends, k, RectCols{});
     }
     timing_mark(ctx, 2, st, false);
     HIPC(hipGetLastError());
@@ -1972,7 +1982,8 @@ int allpairs_sparse_list_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const 
 //
 // The literal Mash merge, one lane per (q, r) pair of `npairs` cells from cell
 // `first` of the call's rectangle (cell t = (q - q0) * N + r): the cross-check
-// of the RECT kernel, and the route for s > 2048 and DREPHIP_AP_MERGE.
+// of the RECT kernels, the route for DREPHIP_AP_MERGE and (s > 2048) for
+// DREPHIP_RECT_BAND_OFF, and the rerun after an unbuildable band table.
 __global__ __launch_bounds__(256) void k_rect_merge(const uint64_t *__restrict__ qhashes,
                                                     const uint32_t *__restrict__ qnhash,
                                                     const uint64_t *__restrict__ rhashes,
@@ -2252,21 +2263,87 @@ static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_
     return rc;
 }
 
+// Rows [q0, q1) through the RECT flavour of the band kernel (launch_band's
+// geometry: R = 4, 2^11 slots, cap 768, two workgroups per CU; no value
+// rounds): the item plan, the launches, then the failure count.  When a band
+// table could not be built (nfail) the rows are rerun by k_rect_merge, as
+// launch_band_cfg reruns the triangle's, and ctx->rect_fallback is set.
+// Synchronises the stream before the rerun; the rerun itself is queued.
+static int launch_rect_band(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q,
+                            const uint64_t *d_rh, const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1,
+                            uint16_t *d_common, uint16_t *d_denom, std::vector<ItemGroup> &groups, hipStream_t st) {
+    constexpr int R = kBandR, BB = 11, CAP = 768, MINW = 8;
+    const uint32_t cap = std::min(std::max(ctx->rect_band_cap, 1u), (uint32_t)CAP);
+    const uint64_t nrt = ((uint64_t)(q1 - q0) + R - 1) / R, nct = ((uint64_t)N + kBandCols - 1) / kBandCols;
+    if (nrt * nct + kXcds * 16ull >= (1ull << 32)) {
+        set_error("the rectangle's item list exceeds 2^32 entries: call it in row ranges");
+        return DREPHIP_ERR_UNSUPPORTED;
+    }
+    int rc;
+    uint2 *d_items = nullptr;
+    uint64_t nitems;
+    if ((rc = expand_items<false>(ctx, plan_rect_items(q0, q1, N, R, kBandCols), groups, "rectb_items", R, kBandCols,
+                                  st, (void **)&d_items, &nitems)))
+        return rc;
+    const uint64_t per = max_blocks(1024);           // items per dispatch
+    if (getenv("DREPHIP_DEBUG"))                    // the geometry this call runs at (the tests read it)
+        fprintf(stderr, "[drephip] rect band plan: R %d C %u cap %u items %llu slots %llu pieces %u\n", R, kBandCols, cap,
+                (unsigned long long)(nrt * nct), (unsigned long long)nitems, (uint32_t)((nitems + per - 1) / per));
+    uint32_t *d_nfail;
+    if ((rc = scratch(ctx, "ap_nfail_band", 4, (void **)&d_nfail))) return rc;
+    HIPC(hipMemsetAsync(d_nfail, 0, 4, st));
+    constexpr size_t lds = band_lds_bytes<R, BB, CAP>();
+    auto kern = k_allpairs_band<R, BB, CAP, 1024, MINW, false, false, true>;
+    HIPC(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const RectCols cols{d_rh, d_rn, N};
+    timing_mark(ctx, 2, st, true);
+    for (uint64_t i0 = 0; i0 < nitems; i0 += per)
+        hipLaunchKernelGGL(kern, dim3((uint32_t)std::min<uint64_t>(nitems - i0, per)), dim3(1024), lds, st, d_qh, d_qn,
+                           ctx->s, Q, q1, cap, d_items + i0, d_common, d_denom, (uint64_t)q0 * N, d_nfail,
+                           (uint64_t *)nullptr, (const uint4 *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                           (const uint64_t *)nullptr, 0u, cols);
+    timing_mark(ctx, 2, st, false);
+    HIPC(hipGetLastError());
+    uint32_t nfail = 0;
+    HIPC(hipMemcpyAsync(&nfail, d_nfail, 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (nfail) {   // a band table could not be built with any field pair: exact merge kernel instead
+        ctx->rect_fallback = 1;
+        return launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
+    }
+    return DREPHIP_OK;
+}
+
 // the rectangle's kernel for this context: the whole-row table kernel when its
-// tables fit (s <= 2048), k_rect_merge otherwise and on request; no band kernel
+// tables fit (s <= 2048); above them the RECT band kernel, or k_rect_merge
+// under DREPHIP_RECT_BAND_OFF.  DREPHIP_RECT_BAND_FORCE: the band kernel at
+// every s under DREPHIP_AP_AUTO.  k_rect_merge on request; DREPHIP_AP_BAND
+// (the triangle's selector) stays unsupported here.  Records the choice as
+// the call's kernel (drephip_last_rect_info).
 static int rect_path(drephip_ctx *ctx, bool force_merge, uint32_t *R, int *path) {
     *R = 1;
     *path = DREPHIP_AP_MERGE;
+    ctx->rect_kernel = DREPHIP_AP_MERGE;
+    ctx->rect_fallback = 0;
     if (force_merge || ctx->ap_path == DREPHIP_AP_MERGE) return DREPHIP_OK;
     if (ctx->ap_path == DREPHIP_AP_BAND) {
-        set_error("the query-against-reference rectangle has no band kernel: DREPHIP_AP_AUTO, _TABLE or _MERGE");
+        set_error("the query-against-reference rectangle does not take DREPHIP_AP_BAND: DREPHIP_AP_AUTO, _TABLE or "
+                  "_MERGE (drephip_set_rect_band selects its band kernel)");
         return DREPHIP_ERR_UNSUPPORTED;
     }
     int p;
     int rc = allpairs_geometry(ctx, R, &p);         // (DREPHIP_AP_TABLE with s > 2048: its error)
     if (rc) return rc;
-    if (p == DREPHIP_AP_TABLE) *path = DREPHIP_AP_TABLE;
-    else *R = 1;                                    // AUTO past the tables: the merge kernel
+    if (ctx->ap_path == DREPHIP_AP_AUTO && ctx->rect_band == DREPHIP_RECT_BAND_FORCE) p = DREPHIP_AP_BAND;
+    if (p == DREPHIP_AP_TABLE) {
+        *path = DREPHIP_AP_TABLE;
+    } else if (ctx->rect_band != DREPHIP_RECT_BAND_OFF) {
+        *path = DREPHIP_AP_BAND;                    // AUTO past the tables (or forced): the band kernel
+        *R = kBandR;
+    } else {
+        *R = 1;                                     // DREPHIP_RECT_BAND_OFF past the tables: the merge kernel
+    }
+    ctx->rect_kernel = *path;
     return DREPHIP_OK;
 }
 
@@ -2286,6 +2363,8 @@ int rect_device_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_q
     std::vector<ItemGroup> groups;                   // lives until the stream sync below
     if (path == DREPHIP_AP_MERGE)
         rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
+    else if (path == DREPHIP_AP_BAND)
+        rc = launch_rect_band(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, d_common, d_denom, groups, st);
     else
         rc = rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, R, d_common, d_denom, nullptr, groups, st);
     if (rc) return rc;
@@ -2338,7 +2417,12 @@ int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_q
         for (uint32_t b0 = q0; b0 < q1;) {
             const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
             const uint64_t cells = (uint64_t)(b1 - b0) * N;
-            if ((rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, cells, d_c, d_d, st))) return rc;
+            // (the band kernel's launch synchronises: `groups` is free for the next block)
+            if (path == DREPHIP_AP_BAND)
+                rc = launch_rect_band(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, d_c, d_d, groups, st);
+            else
+                rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, cells, d_c, d_d, st);
+            if (rc) return rc;
             const uint64_t per = max_blocks(256) * 256;
             for (uint64_t p0 = 0; p0 < cells; p0 += per) {
                 const uint64_t np = std::min(per, cells - p0);
@@ -2386,6 +2470,8 @@ int rect_top_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, 
         std::vector<ItemGroup> groups;               // lives until the block's stream sync
         if (path == DREPHIP_AP_MERGE)
             rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, (uint64_t)(b1 - b0) * N, d_c, d_d, st);
+        else if (path == DREPHIP_AP_BAND)
+            rc = launch_rect_band(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, d_c, d_d, groups, st);
         else
             rc = rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, d_c, d_d, nullptr, groups, st);
         if (rc) return rc;

@@ -189,6 +189,13 @@ DREPHIP_EXPORT int drephip_create(int device, int k, uint32_t s, uint32_t seed, 
                                                                                                 : DREPHIP_LINK_PATH_AUTO;
     if (const char *ip = std::getenv("DREPHIP_INGEST"))         // default ingest path of drephip_sketch_files
         c->ingest_path = !strcmp(ip, "device") ? DREPHIP_INGEST_DEVICE : DREPHIP_INGEST_HOST;
+    if (const char *rb = std::getenv("DREPHIP_RECT_BAND"))      // default band mode of the rectangle (tests, A/B runs)
+        c->rect_band = !strcmp(rb, "off") ? DREPHIP_RECT_BAND_OFF : !strcmp(rb, "force") ? DREPHIP_RECT_BAND_FORCE
+                                                                                          : DREPHIP_RECT_BAND_AUTO;
+    if (const char *rcap = std::getenv("DREPHIP_RECT_BAND_CAP")) {
+        const long v = std::atol(rcap);
+        if (v >= 1 && v <= 1024) c->rect_band_cap = (uint32_t)v;
+    }
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete c; set_error(hipGetErrorString(e)); return DREPHIP_ERR_HIP; }
     *out = c;
@@ -225,6 +232,22 @@ DREPHIP_EXPORT int drephip_set_allpairs_path(drephip_ctx *ctx, int path, uint32_
     if (band_cap < 1 || band_cap > 1024) { set_error("band_cap must be in 1..1024"); return DREPHIP_ERR_ARG; }
     ctx->ap_path = path;
     ctx->band_cap = band_cap;
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_set_rect_band(drephip_ctx *ctx, int mode, uint32_t band_cap) {
+    if (!ctx) { set_error("null context"); return DREPHIP_ERR_ARG; }
+    if (mode < DREPHIP_RECT_BAND_AUTO || mode > DREPHIP_RECT_BAND_FORCE) { set_error("unknown rectangle band mode"); return DREPHIP_ERR_ARG; }
+    if (band_cap < 1 || band_cap > 1024) { set_error("band_cap must be in 1..1024"); return DREPHIP_ERR_ARG; }
+    ctx->rect_band = mode;
+    ctx->rect_band_cap = band_cap;
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_last_rect_info(drephip_ctx *ctx, int *kernel, int *fallback) {
+    if (!ctx) { set_error("null context"); return DREPHIP_ERR_ARG; }
+    if (kernel) *kernel = ctx->rect_kernel;
+    if (fallback) *fallback = ctx->rect_fallback;
     return DREPHIP_OK;
 }
 

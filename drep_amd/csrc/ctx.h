@@ -167,6 +167,10 @@ struct drephip_ctx {
     int link_path = 0;        // DREPHIP_LINK_PATH_*: 0 auto (sparse when it applies, else dense)
     uint32_t band_cap = 1024; // elements per row per band of the banded all-pairs kernel (clamped to its LDS budget)
     uint32_t band_round = 0;  // elements per row per value round of the band kernel (0: no rounds; A/B)
+    int rect_band = 0;        // DREPHIP_RECT_BAND_*: 0 auto (band kernel for s > 2048), 1 off, 2 force
+    uint32_t rect_band_cap = 768; // elements per row per band of the rectangle's band kernel (clamped to 768)
+    int rect_kernel = 0;      // the last rectangle call's counts kernel (DREPHIP_AP_TABLE / _BAND / _MERGE; 0: none yet)
+    int rect_fallback = 0;    // 1: it reran rows by k_rect_merge after an unbuildable band table
     // named grow-only device scratch buffers
     std::map<std::string, DevBuf> bufs;
     // per-kernel timing of the last call: {sum ms, launches}
@@ -315,8 +319,9 @@ uint64_t allpairs_image_bytes_per_row(drephip_ctx *ctx, uint32_t R);
 
 // Query against reference (allpairs.hip): rows [q0, q1) of the Q x N rectangle
 // of the query matrix against the reference matrix, row-major, by the RECT
-// flavour of the whole-row kernel or (force_merge, s > 2048, DREPHIP_AP_MERGE)
-// k_rect_merge.  Blocking.
+// flavour of the whole-row kernel (s <= 2048), the RECT flavour of the band
+// kernel above (ctx->rect_band) or (force_merge, DREPHIP_AP_MERGE,
+// DREPHIP_RECT_BAND_OFF above 2048) k_rect_merge.  Blocking.
 int rect_device_impl(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
                      const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0, uint32_t q1,
                      uint16_t *d_common, uint16_t *d_denom, hipStream_t st, bool force_merge);

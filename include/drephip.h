@@ -485,18 +485,44 @@ int drephip_last_sparse_stats(drephip_ctx *ctx, uint32_t *blocks, uint64_t *dire
  * Q == 0, N == 0 or q0 >= q1: DREPHIP_OK, nothing written.  Null pointers:
  * DREPHIP_ERR_ARG.  Kernels: the RECT flavour of k_allpairs_q (whole-row LDS
  * tables of the query rows, the reference sketches streamed as columns) for
- * s <= 2048 (DREPHIP_AP_AUTO / DREPHIP_AP_TABLE), k_rect_merge (the literal
- * merge, one lane per pair) above and for DREPHIP_AP_MERGE; a context set to
- * DREPHIP_AP_BAND gets DREPHIP_ERR_UNSUPPORTED (no RECT band kernel).  No
+ * s <= 2048 (DREPHIP_AP_AUTO / DREPHIP_AP_TABLE); above, under
+ * DREPHIP_AP_AUTO, the RECT flavour of k_allpairs_band (value bands of the
+ * query rows: R = 4, 2^11 slots, at most 768 elements per row per band, 128
+ * reference columns per item; no value rounds), which reruns the call's rows
+ * by k_rect_merge when a band table cannot be built; k_rect_merge (the
+ * literal merge, one lane per pair) for DREPHIP_AP_MERGE and, above 2048, for
+ * DREPHIP_RECT_BAND_OFF (drephip_set_rect_band below).  A context set to
+ * DREPHIP_AP_BAND, the triangle's selector, gets DREPHIP_ERR_UNSUPPORTED.  No
  * shared-hash screen runs.  Blocking, on the caller's stream; a pending
  * drephip_allpairs_device_async on the context is waited for first.
- * drephip_last_kernel_ms `which` 2 / 3 report the rectangle's kernel and its
- * table build.  The device forms assume well-formed rows. */
+ * drephip_last_kernel_ms `which` 2 / 3 report the rectangle's kernel (the
+ * rerun included) and its table build.  With DREPHIP_DEBUG set the band route
+ * prints one line per call (per row block of the record and best-hit forms):
+ * "[drephip] rect band plan: R 4 C 128 cap .. items .. slots .. pieces .."
+ * (elements per row per band, (row tile, column tile) pairs, item slots with
+ * the idle ones, kernel dispatches).  The device forms assume well-formed
+ * rows. */
 int drephip_dist_rect_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
                              const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0,
                              uint32_t q1, uint16_t *d_common, uint16_t *d_denom /* nullable */, void *stream);
-/* The same rectangle by k_rect_merge whatever s (`mash dist <reference.msh>
- * <query.msh>` by Mash's own loop): the independent cross-check. */
+/* The rectangle's band kernel (s > 2048 under DREPHIP_AP_AUTO).  band_cap:
+ * elements per row per band, 1..1024 (else DREPHIP_ERR_ARG), clamped to 768;
+ * an unknown mode: DREPHIP_ERR_ARG.  A new context takes the mode from the
+ * environment variable DREPHIP_RECT_BAND (auto | off | force) and the cap from
+ * DREPHIP_RECT_BAND_CAP when they are set, read at creation. */
+#define DREPHIP_RECT_BAND_AUTO  0  /* under DREPHIP_AP_AUTO: tables to s = 2048, the band kernel above (the default) */
+#define DREPHIP_RECT_BAND_OFF   1  /* k_rect_merge above the tables, as before the band kernel */
+#define DREPHIP_RECT_BAND_FORCE 2  /* the band kernel at every s (tests: small caps make many bands of small sketches) */
+int drephip_set_rect_band(drephip_ctx *ctx, int mode, uint32_t band_cap /* 1..1024, clamped to 768 */);
+/* The last rectangle call that ran (any drephip_dist_rect* form; an empty call
+ * leaves it): *kernel = the kernel chosen for its counts (DREPHIP_AP_TABLE /
+ * _BAND / _MERGE; 0 before the first call), *fallback = 1 when a band table
+ * could not be built and the call's (or a row block's) rows were rerun by
+ * k_rect_merge.  Either pointer may be NULL. */
+int drephip_last_rect_info(drephip_ctx *ctx, int *kernel, int *fallback);
+/* The same rectangle by k_rect_merge whatever s and whatever the band mode
+ * (`mash dist <reference.msh> <query.msh>` by Mash's own loop): the
+ * independent cross-check. */
 int drephip_dist_rect_merge_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
                                    const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0,
                                    uint32_t q1, uint16_t *d_common, uint16_t *d_denom /* nullable */, void *stream);
@@ -515,7 +541,9 @@ int drephip_dist_rect(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t 
  * kernel stages and appends the records itself, no rectangle is written.
  * Above, and for DREPHIP_AP_MERGE: query-row blocks of at most 2^28 pairs
  * (at least one row; DREPHIP_RECT_BLOCK_ROWS sets fewer rows, for tests),
- * each merged into a scratch rectangle of the context and compacted.  With
+ * each filled into a scratch rectangle of the context by the kernel
+ * drephip_dist_rect_device picks (the RECT band kernel, with its rerun per
+ * block, or k_rect_merge) and compacted.  With
  * DREPHIP_DEBUG set, the RECT kernel's plan is printed to stderr, one line
  * per call: "[drephip] rect plan: R .. C .. items .. slots .. gmax .. pieces
  * .." (row tile, column tile, (row tile, column tile) pairs, item slots with
@@ -545,7 +573,8 @@ int drephip_dist_rect_sparse(drephip_ctx *ctx, const uint64_t *qhashes, const ui
  * nothing written; null pointers: DREPHIP_ERR_ARG.  No Q x N buffer: the
  * query rows are walked in blocks of at most 2^28 cells (at least one row;
  * DREPHIP_RECT_TOP_BLOCK_ROWS sets fewer rows, for tests), each block's counts
- * by the rectangle's kernel (as drephip_dist_rect_device picks it;
+ * by the rectangle's kernel (as drephip_dist_rect_device picks it: tables,
+ * the RECT band kernel above s = 2048 with its rerun per block, or the merge;
  * DREPHIP_AP_BAND: DREPHIP_ERR_UNSUPPORTED) into a scratch rectangle of the
  * context (common + denom, at most 1 GB), then k_rect_top selects per row.
  * Blocking, on the caller's stream; a pending drephip_allpairs_device_async
