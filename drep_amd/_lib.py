@@ -116,6 +116,12 @@ SIGNATURES = {
     "drephip_set_allpairs_path": (C.c_int, [vp, C.c_int, C.c_uint32]),
     "drephip_set_rect_band": (C.c_int, [vp, C.c_int, C.c_uint32]),
     "drephip_last_rect_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "drephip_set_rect_screen": (C.c_int, [vp, C.c_int]),
+    "drephip_last_rect_screen_stats": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                 C.POINTER(C.c_uint32)]),
+    "drephip_last_rect_screen_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "drephip_rect_screen_mode_of": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "drephip_linkage": (C.c_int, [vp, f64p, C.c_uint32, C.c_int, f64p]),
     "drephip_linkage_counts_device": (C.c_int, [vp, vp, vp, C.c_uint32, u32p, f64p, C.c_uint32,
                                                 np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS"),
@@ -510,6 +516,33 @@ class Context:
         k, f = C.c_int(0), C.c_int(0)
         check(lib().drephip_last_rect_info(self._h, C.byref(k), C.byref(f)), "drephip_last_rect_info")
         return k.value, f.value
+
+    # the rectangle's two-set shared-hash screen (include/drephip.h DREPHIP_RECT_SCREEN_*)
+    RECT_SCREEN_AUTO, RECT_SCREEN_OFF, RECT_SCREEN_FORCE = 0, 1, 2
+
+    def set_rect_screen(self, mode: int) -> None:
+        """The screen in front of the query-against-reference kernels: auto
+        (from 4096 references and 2048 query rows on, unless its count pass
+        finds the block too dense), off, or force (any size, no verdict)."""
+        check(lib().drephip_set_rect_screen(self._h, int(mode)), "drephip_set_rect_screen")
+
+    def last_rect_screen_stats(self) -> dict:
+        """{used, blocks, query_entries, distinct, checks, marked, dense_blocks}
+        of the last rectangle call's screen (zeros when it did not run)."""
+        u, b, d = C.c_int(0), C.c_uint32(0), C.c_uint32(0)
+        qe, di, ch, mk = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib().drephip_last_rect_screen_stats(self._h, C.byref(u), C.byref(b), C.byref(qe), C.byref(di),
+                                                   C.byref(ch), C.byref(mk), C.byref(d)),
+              "drephip_last_rect_screen_stats")
+        return {"used": bool(u.value), "blocks": b.value, "query_entries": qe.value, "distinct": di.value,
+                "checks": ch.value, "marked": mk.value, "dense_blocks": d.value}
+
+    def last_rect_screen_ms(self) -> dict:
+        """The screen's phase times (ms) of the last rectangle call, measured
+        while set_timing covers kernel 4: sort, count, mark, lists, fill."""
+        v = (C.c_double * 5)()
+        check(lib().drephip_last_rect_screen_ms(self._h, v), "drephip_last_rect_screen_ms")
+        return dict(zip(("sort", "count", "mark", "lists", "fill"), (float(x) for x in v)))
 
     LINK_METHODS = LINK_METHODS
     # linkage path (include/drephip.h DREPHIP_LINK_PATH_*)

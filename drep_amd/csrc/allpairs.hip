@@ -165,6 +165,13 @@ __global__ __launch_bounds__(1024) void k_build_q32(const uint64_t *__restrict__
     const uint32_t n = nhash[g];
     const uint64_t *A = hashes + (uint64_t)g * s;
     for (uint32_t i = threadIdx.x; i < s; i += blockDim.x) img[2 * H * R + i * R + rr] = (uint32_t)(A[i] >> 32);
+    // A row whose last valid hash is 2^64 - 1 (no sketcher admits it: it is the
+    // padding value) would match the padding of every partial column: its
+    // pairs are merged literally, as a failed row's are.
+    if (n > 0 && A[n - 1] == kEmpty) {
+        if (threadIdx.x == 0) fam_out[r] = kFamFailed;
+        return;
+    }
     for (uint32_t fam = 0; fam < kMaxFam; fam++) {
         const QFields q = qfields(fam);
         for (uint32_t i = threadIdx.x; i < 2 * H; i += blockDim.x) Tb[i] = empty_word(i, hm);
@@ -798,7 +805,11 @@ __host__ __device__ constexpr size_t q_lds_bytes(uint32_t R, uint32_t TS, uint32
 // nhash: the query matrix, whose images k_build_q32 built) and the columns the
 // rc.n sketches of the reference matrix rc; items are {i0, c0, cend, 0} over
 // every (row tile, column tile) pair, the output the (row1 - row0) x rc.n
-// rectangle, row-major.  No screen: neither LIST nor chunk masks.
+// rectangle, row-major.  RECT, LIST (the rectangle's two-set screen,
+// rect_screen.hip): items are {i0, list offset, count, 0}, clist holds
+// reference indices; the dense form writes its listed cells only (the screen's
+// fill wrote the others), the SPARSE form stages records as RECT, SPARSE does.
+// No chunk masks.
 struct RectCols {
     const uint64_t *hashes = nullptr;
     const uint32_t *nhash = nullptr;
@@ -812,7 +823,6 @@ __global__ __launch_bounds__(kApWG, MINW) void k_allpairs_q(
     uint16_t *__restrict__ common, uint16_t *__restrict__ denom, uint64_t seg0, const uint32_t *__restrict__ clist,
     int hitq, const uint32_t *__restrict__ cmask, SparseOut sp, RectCols rc = RectCols{}) {
     static_assert(LIST || RECT || !SPARSE, "the SPARSE flavour runs on the screened lists or the rectangle");
-    static_assert(!(RECT && LIST), "the rectangle has no screen");
     // the column side: the matrix itself, or (RECT) the reference matrix
     const uint64_t *__restrict__ chashes = RECT ? rc.hashes : hashes;
     const uint32_t *__restrict__ cnhash = RECT ? rc.nhash : nhash;
@@ -1150,7 +1160,9 @@ enum : uint32_t { kBsDone = 1u };
 // RECT (drephip_dist_rect_device, s > 2048): the rows [.., row1) are queries
 // (hashes, nhash, N = Q), the columns the reference matrix rc; no diagonal --
 // every column of the item is live and every cell is written, pair (q, r) at
-// q * rc.n + r - seg0 (seg0 = q0 * rc.n).  Neither LIST nor ROUNDS.
+// q * rc.n + r - seg0 (seg0 = q0 * rc.n).  No ROUNDS.  RECT, LIST (the
+// rectangle's two-set screen): every listed column is live and the epilogue
+// writes the listed cells only.
 template <int R, int BB, int CAP, int WG, int MINW, bool LIST = false, bool ROUNDS = false, bool RECT = false>
 __global__ __launch_bounds__(WG, MINW) void k_allpairs_band(
     const uint64_t *__restrict__ hashes, const uint32_t *__restrict__ nhash, uint32_t s, uint32_t N,
@@ -1161,7 +1173,7 @@ __global__ __launch_bounds__(WG, MINW) void k_allpairs_band(
     constexpr uint32_t H = 1u << BB, hm = H - 1, TS = 2 * H;
     constexpr uint32_t NW = WG / 64;
     static_assert(CAP < H, "band positions stay below the empty word's position hm");
-    static_assert(!(RECT && (LIST || ROUNDS)), "the rectangle has neither a screen nor value rounds");
+    static_assert(!(RECT && ROUNDS), "the rectangle has no value rounds");
     // the column side: the matrix itself, or (RECT) the reference matrix
     const uint64_t *__restrict__ chashes = RECT ? rc.hashes : hashes;
     const uint32_t *__restrict__ cnhash = RECT ? rc.nhash : nhash;
@@ -1354,10 +1366,10 @@ __global__ __launch_bounds__(WG, MINW) void k_allpairs_band(
             uint32_t nl = 0;
 #pragma unroll
             for (int rr = 0; rr < R; rr++) if ((uint32_t)rr == r) nl = nA[rr];
-            const uint64_t o = cond_index(i, c, N) - seg0;
+            const uint64_t o = (RECT ? (uint64_t)i * Nc + c : cond_index(i, c, N)) - seg0;
             common[o] = (uint16_t)pcnt[r * kBandCols + ci];
             if (denom) {
-                const uint32_t nB = nhash[c];
+                const uint32_t nB = cnhash[c];
                 uint32_t dd = s;
                 if (any_partial_row || nB < s) {
                     const uint32_t u = nl + nB - pm[r * kBandCols + ci];
@@ -2108,6 +2120,16 @@ __global__ __launch_bounds__(kTopWG) void k_rect_top(const uint16_t *__restrict_
     }
 }
 
+// flag = 1 when a query row of [q0, q1) ends in the valid hash 2^64 - 1
+__global__ __launch_bounds__(256) void k_rect_last_is_max(const uint64_t *__restrict__ qhashes,
+                                                          const uint32_t *__restrict__ qnhash, uint32_t s, uint32_t q0,
+                                                          uint32_t q1, uint32_t *__restrict__ flag) {
+    const uint32_t q = q0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= q1) return;
+    const uint32_t n = min(qnhash[q], s);
+    if (n > 0 && qhashes[(uint64_t)q * s + n - 1] == kEmpty) *flag = 1u;
+}
+
 static int launch_rect_merge(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, const uint64_t *d_rh,
                              const uint32_t *d_rn, uint32_t N, uint32_t q0, uint64_t cells, uint16_t *d_common,
                              uint16_t *d_denom, hipStream_t st) {
@@ -2159,20 +2181,37 @@ static ItemPlan plan_rect_items(uint32_t q0, uint32_t q1, uint32_t Nc, uint32_t 
     return p;
 }
 
-template <int R, int NCH, int MINW, bool SPARSE>
+// DREPHIP_DEBUG: the geometry a screened block runs at (the tests read it);
+// the items are read back to count the real ones among the idle slots
+static int rect_screen_plan_line(drephip_ctx *ctx, const ScreenResult &scr, uint32_t nrows, uint32_t R, uint32_t C,
+                                 uint32_t per, hipStream_t st) {
+    if (!getenv("DREPHIP_DEBUG")) return DREPHIP_OK;
+    std::vector<uint4> h(scr.nitems);
+    HIPC(hipStreamSynchronize(st));
+    if (scr.nitems) HIPC(hipMemcpy(h.data(), scr.items, scr.nitems * sizeof(uint4), hipMemcpyDeviceToHost));
+    uint64_t items = 0;
+    for (const uint4 &it : h) items += it.x != kIdleItem;
+    fprintf(stderr, "[drephip] rect screen plan: R %u C %u tiles %u marked %llu items %llu slots %u pieces %u\n", R, C,
+            (nrows + R - 1) / R, (unsigned long long)scr.marked, (unsigned long long)items, scr.nitems,
+            (scr.nitems + per - 1) / per);
+    return DREPHIP_OK;
+}
+
+// LIST: the two-set screen's items / column list (clist)
+template <int R, int NCH, int MINW, bool SPARSE, bool LIST = false>
 static int launch_rect_q(drephip_ctx *ctx, uint32_t nitems, size_t lds, hipStream_t st, const uint64_t *qh,
                          const uint32_t *qn, const uint32_t *blk, uint32_t stride, const uint8_t *fam, uint32_t Q,
                          uint32_t q0, uint32_t q1, uint32_t B, const uint4 *items, uint16_t *cm, uint16_t *dn,
-                         const RectCols &rc, const SparseOut &sp) {
-    HIPC(hipFuncSetAttribute((const void *)k_allpairs_q<R, NCH, MINW, false, SPARSE, true>,
+                         const RectCols &rc, const SparseOut &sp, const uint32_t *clist = nullptr) {
+    HIPC(hipFuncSetAttribute((const void *)k_allpairs_q<R, NCH, MINW, LIST, SPARSE, true>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const char *he = getenv("DREPHIP_AP_HIT");         // as launch_q
     const int hitq = he ? atoi(he) : 1;
     timing_mark(ctx, 2, st, true);
     for (uint32_t i0 = 0; i0 < nitems; i0 += (uint32_t)max_blocks(kApWG))
-        hipLaunchKernelGGL((k_allpairs_q<R, NCH, MINW, false, SPARSE, true>),
+        hipLaunchKernelGGL((k_allpairs_q<R, NCH, MINW, LIST, SPARSE, true>),
                            dim3(std::min<uint32_t>(nitems - i0, (uint32_t)max_blocks(kApWG))), dim3(kApWG), lds, st, qh,
-                           qn, blk, stride, fam, ctx->s, Q, q0, q1, B, items + i0, cm, dn, 0ull, nullptr, hitq, nullptr,
+                           qn, blk, stride, fam, ctx->s, Q, q0, q1, B, items + i0, cm, dn, 0ull, clist, hitq, nullptr,
                            sp, rc);
     timing_mark(ctx, 2, st, false);
     HIPC(hipGetLastError());
@@ -2182,9 +2221,15 @@ static int launch_rect_q(drephip_ctx *ctx, uint32_t nitems, size_t lds, hipStrea
 // Rows [q0, q1) through the RECT flavour of the whole-row kernel: the query
 // rows' images by k_build_q32, the item plan, the launch.  sp == null: the
 // rectangle into d_common / d_denom; else records into *sp.  Queued on st.
+// scr (the two-set screen's lists of these rows, rect_screen.hip): the LIST
+// flavours over its items instead of the plan -- the geometries of
+// rect_list_geometry only; nothing is launched when no cell is marked.
 static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
                       const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint32_t R, uint16_t *d_common,
-                      uint16_t *d_denom, const SparseOut *sp, std::vector<ItemGroup> &groups, hipStream_t st) {
+                      uint16_t *d_denom, const SparseOut *sp, std::vector<ItemGroup> &groups, hipStream_t st,
+                      const ScreenResult *scr = nullptr) {
+    if (scr && rect_screen_plan_line(ctx, *scr, q1 - q0, R, kApCols, (uint32_t)max_blocks(kApWG), st)) return DREPHIP_ERR_HIP;
+    if (scr && scr->nitems == 0) return DREPHIP_OK;
     const uint32_t s = ctx->s;
     uint32_t B = 4;
     while ((1u << B) < 2 * s) B++;
@@ -2205,6 +2250,29 @@ static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_
                        d_fam);
     timing_mark(ctx, 3, st, false);
     HIPC(hipGetLastError());
+    const size_t lds = (size_t)stride * 4;
+    const uint32_t nch = (s + 63) / 64;
+    const bool two = lds <= 80 * 1024;              // two workgroups per CU when the LDS allows
+    const RectCols cols{d_rh, d_rn, N};
+    const SparseOut out = sp ? *sp : SparseOut{};
+    if (scr) {
+        // the LIST flavours exist at the geometries allpairs_geometry picks by
+        // itself (rect_list_geometry; the caller has checked)
+        const uint32_t ni = scr->nitems;
+        const uint4 *li = scr->items;
+#define DREPHIP_QL(RR, NC, MW) (sp ? launch_rect_q<RR, NC, MW, true, true>(ctx, ni, lds, st, d_qh, d_qn, d_blk, stride, d_fam, Q, q0, q1, B, \
+                                                                          li, d_common, d_denom, cols, out, scr->clist)      \
+                                   : launch_rect_q<RR, NC, MW, false, true>(ctx, ni, lds, st, d_qh, d_qn, d_blk, stride, d_fam, Q, q0, q1, \
+                                                                           B, li, d_common, d_denom, cols, out, scr->clist))
+        if (R == 8 && nch <= 8 && two) return DREPHIP_QL(8, 8, 8);
+        if (R == 8 && nch > 8 && nch <= 16 && !two) return DREPHIP_QL(8, 16, 4);
+        if (R == 4 && nch > 8 && nch <= 16 && two) return DREPHIP_QL(4, 16, 8);
+        if (R == 4 && nch > 16 && !two) return DREPHIP_QL(4, 32, 4);
+        if (R == 2 && nch > 16 && two) return DREPHIP_QL(2, 32, 8);
+#undef DREPHIP_QL
+        set_error("the screened rectangle has no kernel at this geometry");
+        return DREPHIP_ERR_UNSUPPORTED;
+    }
     // column tile: the rule of the triangle's plan -- the widest (<= kApCols)
     // that still gives every workgroup slot of the chip about four items
     uint32_t C = kApCols;
@@ -2228,11 +2296,6 @@ static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_
                 (unsigned long long)nitems_for(C), (unsigned long long)ni64, (unsigned long long)gmax,
                 (uint32_t)((ni64 + per - 1) / per));
     }
-    const size_t lds = (size_t)stride * 4;
-    const uint32_t nch = (s + 63) / 64;
-    const bool two = lds <= 80 * 1024;              // two workgroups per CU when the LDS allows
-    const RectCols cols{d_rh, d_rn, N};
-    const SparseOut out = sp ? *sp : SparseOut{};
 #define DREPHIP_QR1(RR, NC, MW, SP) launch_rect_q<RR, NC, MW, SP>(ctx, ni, lds, st, d_qh, d_qn, d_blk, stride, d_fam, Q, q0, q1, B, \
                                                                   d_items, d_common, d_denom, cols, out)
 #define DREPHIP_QR(RR, NC) (two ? (sp ? DREPHIP_QR1(RR, NC, 8, true) : DREPHIP_QR1(RR, NC, 8, false)) \
@@ -2269,11 +2332,61 @@ static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_
 // table could not be built (nfail) the rows are rerun by k_rect_merge, as
 // launch_band_cfg reruns the triangle's, and ctx->rect_fallback is set.
 // Synchronises the stream before the rerun; the rerun itself is queued.
+// scr (the two-set screen's lists of these rows): the RECT, LIST flavour over
+// its items; a rerun still writes every cell of the rows.
 static int launch_rect_band(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q,
                             const uint64_t *d_rh, const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1,
-                            uint16_t *d_common, uint16_t *d_denom, std::vector<ItemGroup> &groups, hipStream_t st) {
+                            uint16_t *d_common, uint16_t *d_denom, std::vector<ItemGroup> &groups, hipStream_t st,
+                            const ScreenResult *scr = nullptr) {
     constexpr int R = kBandR, BB = 11, CAP = 768, MINW = 8;
     const uint32_t cap = std::min(std::max(ctx->rect_band_cap, 1u), (uint32_t)CAP);
+    {   // A query row whose last valid hash is 2^64 - 1 (the padding value; no
+        // sketcher admits it) has no band bound above it (maxlast + 1 wraps):
+        // such rows never reach the band kernel, the call's rows go to the
+        // exact merge kernel as after an unbuildable table.
+        uint32_t *d_max, h_max = 0;
+        int rc;
+        if ((rc = scratch(ctx, "rect_last_max", 4, (void **)&d_max))) return rc;
+        HIPC(hipMemsetAsync(d_max, 0, 4, st));
+        hipLaunchKernelGGL(k_rect_last_is_max, dim3((q1 - q0 + 255) / 256), dim3(256), 0, st, d_qh, d_qn, ctx->s, q0, q1,
+                           d_max);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(&h_max, d_max, 4, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        if (h_max) {
+            ctx->rect_fallback = 1;
+            return launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
+        }
+    }
+    if (scr) {
+        int rc;
+        const uint64_t per = max_blocks(1024);       // items per dispatch
+        if ((rc = rect_screen_plan_line(ctx, *scr, q1 - q0, R, kBandCols, (uint32_t)per, st))) return rc;
+        if (scr->nitems == 0) return DREPHIP_OK;
+        uint32_t *d_nfail;
+        if ((rc = scratch(ctx, "ap_nfail_band", 4, (void **)&d_nfail))) return rc;
+        HIPC(hipMemsetAsync(d_nfail, 0, 4, st));
+        constexpr size_t lds = band_lds_bytes<R, BB, CAP>();
+        auto kern = k_allpairs_band<R, BB, CAP, 1024, MINW, true, false, true>;
+        HIPC(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const RectCols cols{d_rh, d_rn, N};
+        timing_mark(ctx, 2, st, true);
+        for (uint64_t i0 = 0; i0 < scr->nitems; i0 += per)
+            hipLaunchKernelGGL(kern, dim3((uint32_t)std::min<uint64_t>(scr->nitems - i0, per)), dim3(1024), lds, st, d_qh,
+                               d_qn, ctx->s, Q, q1, cap, (const uint2 *)nullptr, d_common, d_denom, (uint64_t)q0 * N,
+                               d_nfail, (uint64_t *)nullptr, scr->items + i0, scr->clist, (uint32_t *)nullptr,
+                               (const uint64_t *)nullptr, 0u, cols);
+        timing_mark(ctx, 2, st, false);
+        HIPC(hipGetLastError());
+        uint32_t nfail = 0;
+        HIPC(hipMemcpyAsync(&nfail, d_nfail, 4, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        if (nfail) {   // as below: the rows again by the exact merge kernel, every cell of them
+            ctx->rect_fallback = 1;
+            return launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
+        }
+        return DREPHIP_OK;
+    }
     const uint64_t nrt = ((uint64_t)(q1 - q0) + R - 1) / R, nct = ((uint64_t)N + kBandCols - 1) / kBandCols;
     if (nrt * nct + kXcds * 16ull >= (1ull << 32)) {
         set_error("the rectangle's item list exceeds 2^32 entries: call it in row ranges");
@@ -2347,6 +2460,70 @@ static int rect_path(drephip_ctx *ctx, bool force_merge, uint32_t *R, int *path)
     return DREPHIP_OK;
 }
 
+// ---- the two-set screen (rect_screen.hip) in front of the RECT kernels
+// query rows of a call from which the screen runs (auto).  Measured
+// (profiles/rect_screen.json, N = 10^5, s = 1000): the count pass and the
+// marking each cost 4 ms at 256 rows, 6-8 ms at 1000, 15-20 ms at 10^4, the
+// unscreened kernel 0.013 ms per row; AUTO breaks even near 1100 rows.
+constexpr uint32_t kRectScreenMinQ = 2048;
+
+// The RECT, LIST flavours of k_allpairs_q are instantiated at the (R, chunks,
+// workgroups per CU) allpairs_geometry picks by itself for some s <= 2048 --
+// (8, 8, 2), (8, 16, 1), (4, 16, 2), (4, 32, 1), (2, 32, 2); an A/B override of
+// R (DREPHIP_AP_R) outside them keeps the unscreened plan.
+static bool rect_list_geometry(drephip_ctx *ctx, uint32_t R, int path) {
+    if (path == DREPHIP_AP_BAND) return true;
+    const uint32_t s = ctx->s, nch = (s + 63) / 64;
+    uint32_t B = 4;
+    while ((1u << B) < 2 * s) B++;
+    const bool two = ((q_lds_bytes(R, 2u << B, s) / 4 + 3) & ~3ull) * 4 <= 80 * 1024;
+    return (R == 8 && nch <= 8 && two) || (R == 8 && nch > 8 && nch <= 16 && !two) ||
+           (R == 4 && nch > 8 && nch <= 16 && two) || (R == 4 && nch > 16 && !two) || (R == 2 && nch > 16 && two);
+}
+
+// Whether a call over `rows` query rows screens its blocks: never the merge
+// kernel; DREPHIP_RECT_SCREEN_FORCE at any size (*force: no verdict either);
+// AUTO from kScreenMinN references and kRectScreenMinQ query rows on
+// (DREPHIP_RECT_SCREEN_MIN_N / _MIN_Q lower the floors, for tests).
+static bool rect_screen_on(drephip_ctx *ctx, uint32_t N, uint32_t rows, uint32_t R, int path, bool *force) {
+    *force = false;
+    if (path == DREPHIP_AP_MERGE || ctx->rect_screen_mode == DREPHIP_RECT_SCREEN_OFF) return false;
+    if (!rect_list_geometry(ctx, R, path)) return false;
+    if (ctx->rect_screen_mode == DREPHIP_RECT_SCREEN_FORCE) { *force = true; return true; }
+    const char *mn = getenv("DREPHIP_RECT_SCREEN_MIN_N"), *mq = getenv("DREPHIP_RECT_SCREEN_MIN_Q");
+    const uint32_t min_n = mn ? (uint32_t)atoi(mn) : kScreenMinN, min_q = mq ? (uint32_t)atoi(mq) : kRectScreenMinQ;
+    return N >= min_n && rows >= min_q;
+}
+
+// One block of query rows [b0, b1) by the call's kernel.  d_c / d_d: the
+// block's first row of the rectangle (null with records from the table
+// kernel, sp).  screened: the two-set screen first; when it keeps the block,
+// the rectangle is filled as no-shared-hash cells (denominators only with
+// fill_denom) and the LIST flavour runs on the marked cells, else -- the
+// verdict, or lists past their indices -- every item runs as without it.
+static int rect_block(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
+                      const uint32_t *d_rn, uint32_t N, uint32_t b0, uint32_t b1, uint32_t R, int path, uint16_t *d_c,
+                      uint16_t *d_d, const SparseOut *sp, bool screened, bool force, bool fill_denom,
+                      std::vector<ItemGroup> &groups, hipStream_t st) {
+    if (path == DREPHIP_AP_MERGE)
+        return launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, (uint64_t)(b1 - b0) * N, d_c, d_d, st);
+    ScreenResult scr;
+    const ScreenResult *use = nullptr;
+    int rc;
+    if (screened) {
+        if ((rc = rect_screen_block(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, b1, R,
+                                    path == DREPHIP_AP_BAND ? kBandCols : kApCols, force, st, &scr)))
+            return rc;
+        if (scr.use) {
+            use = &scr;
+            if (d_c && (rc = rect_screen_fill(ctx, d_qn, d_rn, N, b0, b1, d_c, fill_denom ? d_d : nullptr, st))) return rc;
+        }
+    }
+    if (path == DREPHIP_AP_BAND)
+        return launch_rect_band(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, d_c, d_d, groups, st, use);
+    return rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, d_c, d_d, sp, groups, st, use);
+}
+
 int rect_device_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
                      const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint16_t *d_common,
                      uint16_t *d_denom, hipStream_t st, bool force_merge) {
@@ -2360,6 +2537,23 @@ int rect_device_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_q
     int path, rc;
     if ((rc = rect_path(ctx, force_merge, &R, &path))) return rc;
     ctx->last_screen = ScreenResult{};
+    ctx->rect_screen = RectScreenStats{};
+    bool force;
+    if (rect_screen_on(ctx, N, q1 - q0, R, path, &force)) {
+        // screened: blocks of query rows whose bitmap and sort stay bounded
+        const uint32_t rows = rect_screen_block_rows(ctx, N, R);
+        for (uint32_t b0 = q0; b0 < q1;) {
+            const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
+            std::vector<ItemGroup> groups;           // lives until the block's stream sync
+            const uint64_t o = (uint64_t)(b0 - q0) * N;
+            if ((rc = rect_block(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, path, d_common + o,
+                                 d_denom ? d_denom + o : nullptr, nullptr, true, force, true, groups, st)))
+                return rc;
+            HIPC(hipStreamSynchronize(st));
+            b0 = b1;
+        }
+        return DREPHIP_OK;
+    }
     std::vector<ItemGroup> groups;                   // lives until the stream sync below
     if (path == DREPHIP_AP_MERGE)
         rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
@@ -2398,6 +2592,9 @@ int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_q
     int path, rc;
     if ((rc = rect_path(ctx, false, &R, &path))) return rc;
     ctx->last_screen = ScreenResult{};
+    ctx->rect_screen = RectScreenStats{};
+    bool force;
+    const bool screened = rect_screen_on(ctx, N, q1 - q0, R, path, &force);
     unsigned long long *d_count;
     uint64_t *h_tot;
     if ((rc = scratch(ctx, "sp_count", 8, (void **)&d_count))) return rc;
@@ -2405,11 +2602,24 @@ int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_q
     HIPC(hipMemsetAsync(d_count, 0, 8, st));
     const SparseOut out{d_pairs, d_count, cap};
     std::vector<ItemGroup> groups;                   // lives until the stream sync below
-    if (path == DREPHIP_AP_TABLE) {
+    if (path == DREPHIP_AP_TABLE && screened) {
+        // the screen's row blocks; the LIST, SPARSE kernel appends straight from the lists
+        const uint32_t rows = rect_screen_block_rows(ctx, N, R);
+        for (uint32_t b0 = q0; b0 < q1;) {
+            const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
+            if ((rc = rect_block(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, path, nullptr, nullptr, &out, true, force,
+                                 false, groups, st)))
+                return rc;
+            HIPC(hipStreamSynchronize(st));          // `groups` is free for the next block
+            b0 = b1;
+        }
+    } else if (path == DREPHIP_AP_TABLE) {
         if ((rc = rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, R, nullptr, nullptr, &out, groups, st))) return rc;
     } else {
-        // query-row blocks of at most kRectBlockPairs cells (at least one row)
-        const uint32_t rows = rect_block_rows(N, "DREPHIP_RECT_BLOCK_ROWS");
+        // query-row blocks of at most kRectBlockPairs cells (at least one row);
+        // screened: also within the screen's own block bound -- one loop
+        uint32_t rows = rect_block_rows(N, "DREPHIP_RECT_BLOCK_ROWS");
+        if (screened) rows = std::min(rows, rect_screen_block_rows(ctx, N, R));
         const uint64_t bcells = (uint64_t)std::min<uint32_t>(rows, q1 - q0) * N;
         uint16_t *d_c, *d_d;
         if ((rc = scratch(ctx, "rect_blk_common", bcells * 2, (void **)&d_c))) return rc;
@@ -2417,12 +2627,12 @@ int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_q
         for (uint32_t b0 = q0; b0 < q1;) {
             const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
             const uint64_t cells = (uint64_t)(b1 - b0) * N;
-            // (the band kernel's launch synchronises: `groups` is free for the next block)
-            if (path == DREPHIP_AP_BAND)
-                rc = launch_rect_band(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, d_c, d_d, groups, st);
-            else
-                rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, cells, d_c, d_d, st);
-            if (rc) return rc;
+            // (the band kernel's launch synchronises: `groups` is free for the next block);
+            // a screened block is filled with zero counts only: the compaction
+            // reads a denominator where the count is not zero, a listed cell
+            if ((rc = rect_block(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, path, d_c, d_d, nullptr, screened, force,
+                                 false, groups, st)))
+                return rc;
             const uint64_t per = max_blocks(256) * 256;
             for (uint64_t p0 = 0; p0 < cells; p0 += per) {
                 const uint64_t np = std::min(per, cells - p0);
@@ -2457,9 +2667,14 @@ int rect_top_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, 
     int path, rc;
     if ((rc = rect_path(ctx, false, &R, &path))) return rc;
     ctx->last_screen = ScreenResult{};
+    ctx->rect_screen = RectScreenStats{};
+    bool force;
+    const bool screened = rect_screen_on(ctx, N, q1 - q0, R, path, &force);
     // query-row blocks of at most kRectBlockPairs cells (at least one row), as
-    // the record form's merge route
-    const uint32_t rows = rect_block_rows(N, "DREPHIP_RECT_TOP_BLOCK_ROWS");
+    // the record form's merge route; screened: also within the screen's own
+    // block bound -- one loop
+    uint32_t rows = rect_block_rows(N, "DREPHIP_RECT_TOP_BLOCK_ROWS");
+    if (screened) rows = std::min(rows, rect_screen_block_rows(ctx, N, R));
     const uint64_t bcells = (uint64_t)std::min<uint32_t>(rows, q1 - q0) * N;
     uint16_t *d_c, *d_d;
     // 16 bytes more: k_rect_top reads whole 16-byte words up to the last row's end
@@ -2468,13 +2683,9 @@ int rect_top_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, 
     for (uint32_t b0 = q0; b0 < q1;) {
         const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
         std::vector<ItemGroup> groups;               // lives until the block's stream sync
-        if (path == DREPHIP_AP_MERGE)
-            rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, (uint64_t)(b1 - b0) * N, d_c, d_d, st);
-        else if (path == DREPHIP_AP_BAND)
-            rc = launch_rect_band(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, d_c, d_d, groups, st);
-        else
-            rc = rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, d_c, d_d, nullptr, groups, st);
-        if (rc) return rc;
+        if ((rc = rect_block(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, path, d_c, d_d, nullptr, screened, force, true,
+                             groups, st)))
+            return rc;
         timing_mark(ctx, 5, st, true);
         hipLaunchKernelGGL(k_rect_top, dim3((uint32_t)std::min<uint64_t>(b1 - b0, max_blocks(kTopWG))), dim3(kTopWG), 0, st,
                            d_c, d_d, N, b1 - b0, top, d_hits + (uint64_t)(b0 - q0) * top * 4, d_count + (b0 - q0));

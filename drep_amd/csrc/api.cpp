@@ -196,6 +196,8 @@ DREPHIP_EXPORT int drephip_create(int device, int k, uint32_t s, uint32_t seed, 
         const long v = std::atol(rcap);
         if (v >= 1 && v <= 1024) c->rect_band_cap = (uint32_t)v;
     }
+    if (const char *rs = std::getenv("DREPHIP_RECT_SCREEN"))    // default mode of the rectangle's two-set screen
+        (void)drephip_rect_screen_mode_of(rs, &c->rect_screen_mode);
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete c; set_error(hipGetErrorString(e)); return DREPHIP_ERR_HIP; }
     *out = c;
@@ -241,6 +243,41 @@ DREPHIP_EXPORT int drephip_set_rect_band(drephip_ctx *ctx, int mode, uint32_t ba
     if (band_cap < 1 || band_cap > 1024) { set_error("band_cap must be in 1..1024"); return DREPHIP_ERR_ARG; }
     ctx->rect_band = mode;
     ctx->rect_band_cap = band_cap;
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_rect_screen_mode_of(const char *text, int *mode) {
+    if (!text || !mode) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    *mode = !strcmp(text, "off") ? DREPHIP_RECT_SCREEN_OFF : !strcmp(text, "force") ? DREPHIP_RECT_SCREEN_FORCE
+                                                                                    : DREPHIP_RECT_SCREEN_AUTO;
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_set_rect_screen(drephip_ctx *ctx, int mode) {
+    if (!ctx) { set_error("null context"); return DREPHIP_ERR_ARG; }
+    if (mode < DREPHIP_RECT_SCREEN_AUTO || mode > DREPHIP_RECT_SCREEN_FORCE) { set_error("unknown rectangle screen mode"); return DREPHIP_ERR_ARG; }
+    ctx->rect_screen_mode = mode;
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_last_rect_screen_stats(drephip_ctx *ctx, int *used, uint32_t *blocks, uint64_t *query_entries,
+                                                  uint64_t *distinct, uint64_t *checks, uint64_t *marked,
+                                                  uint32_t *dense_blocks) {
+    if (!ctx) { set_error("null context"); return DREPHIP_ERR_ARG; }
+    const RectScreenStats &r = ctx->rect_screen;
+    if (used) *used = r.used;
+    if (blocks) *blocks = r.blocks;
+    if (query_entries) *query_entries = r.query_entries;
+    if (distinct) *distinct = r.distinct;
+    if (checks) *checks = r.checks;
+    if (marked) *marked = r.marked;
+    if (dense_blocks) *dense_blocks = r.dense_blocks;
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_last_rect_screen_ms(drephip_ctx *ctx, double ms[5]) {
+    if (!ctx || !ms) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    for (int i = 0; i < 5; i++) ms[i] = ctx->rect_screen.phase_ms[i];
     return DREPHIP_OK;
 }
 

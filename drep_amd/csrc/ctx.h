@@ -4,6 +4,8 @@
 #include "common.h"
 
 #include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <utility>
@@ -148,6 +150,19 @@ struct SparseStats {
     uint64_t scratch_bytes = 0;   // context scratch after the call (grow-only: its peak)
 };
 
+// The two-set screen of the last rectangle call (rect_screen.hip), summed over
+// its query-row blocks.
+struct RectScreenStats {
+    int used = 0;                 // 1: at least one block ran the LIST kernels on its marked cells only
+    uint32_t blocks = 0;          // query-row blocks the screen looked at
+    uint64_t query_entries = 0;   // query entries sorted
+    uint64_t distinct = 0;        // distinct query hashes (per block, summed)
+    uint64_t checks = 0;          // the count pass's sum of hit runs' lengths (0 under FORCE: no verdict)
+    uint64_t marked = 0;          // marked (row tile, reference) cells of the screened blocks
+    uint32_t dense_blocks = 0;    // blocks the verdict sent to the unscreened plan
+    double phase_ms[5] = {0, 0, 0, 0, 0};   // sort, count pass, marking, lists, fill (timing bit 4 set)
+};
+
 // A run of all-pairs work items (allpairs.hip, plan_items): `size` row tiles
 // from i0 (step R) against column tile c0, at offset `off` of its XCD's list.
 struct ApItemGroup { uint32_t i0, c0, off, size; };
@@ -171,6 +186,8 @@ struct drephip_ctx {
     uint32_t rect_band_cap = 768; // elements per row per band of the rectangle's band kernel (clamped to 768)
     int rect_kernel = 0;      // the last rectangle call's counts kernel (DREPHIP_AP_TABLE / _BAND / _MERGE; 0: none yet)
     int rect_fallback = 0;    // 1: it reran rows by k_rect_merge after an unbuildable band table
+    int rect_screen_mode = 0; // DREPHIP_RECT_SCREEN_*: 0 auto, 1 off, 2 force
+    RectScreenStats rect_screen;  // the last rectangle call's two-set screen
     // named grow-only device scratch buffers
     std::map<std::string, DevBuf> bufs;
     // per-kernel timing of the last call: {sum ms, launches}
@@ -297,6 +314,52 @@ bool screen_applies(drephip_ctx *ctx, uint32_t N);
 // min(s, |A| + |B|); the LIST kernels then overwrite the screened pairs.
 int screen_fill_impl(drephip_ctx *ctx, const uint32_t *d_nhash, uint32_t N, uint32_t row0, uint32_t row1,
                      uint64_t seg0, uint64_t npairs, uint16_t *d_common, uint16_t *d_denom, hipStream_t st);
+
+// DREPHIP_SCREEN_PROF=1: HIP events between the phases, printed to stderr
+struct ScreenProf {
+    bool on = getenv("DREPHIP_SCREEN_PROF") != nullptr;
+    std::vector<std::pair<const char *, hipEvent_t>> ev;
+    void mark(const char *name, hipStream_t st) {
+        if (!on) return;
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, st);
+        ev.push_back({name, e});
+    }
+    ~ScreenProf() {
+        if (!on || ev.empty()) return;
+        (void)hipEventSynchronize(ev.back().second);
+        fprintf(stderr, "[drephip] screen phases (ms):");
+        for (size_t i = 1; i < ev.size(); i++) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev[i - 1].second, ev[i].second);
+            fprintf(stderr, " %s %.3f", ev[i].first, ms);
+        }
+        fprintf(stderr, "\n");
+        for (auto &p : ev) (void)hipEventDestroy(p.second);
+    }
+};
+
+// marked cells (d_bl: [ntiles][NW] words, row tiles of R rows from row0) ->
+// each row tile's ascending column list and the LIST items of at most C
+// columns, XCD-placed (screen.hip).  d_nsimple: the device count read back into
+// res->simple.  res->use stays false when the lists outgrow their 32-bit
+// indices.  Synchronises the stream.
+int screen_lists(drephip_ctx *ctx, const uint32_t *d_bl, uint32_t ntiles, uint32_t NW, uint32_t C, uint32_t row0,
+                 uint32_t R, const unsigned long long *d_nsimple, hipStream_t st, ScreenProf &prof, ScreenResult *res);
+
+// The rectangle's two-set screen (rect_screen.hip).  rect_screen_block: query
+// rows [b0, b1) joined against the reference matrix; res->use: the LIST items
+// (row tiles of R rows from b0, at most C columns each) replace the block's
+// item plan, the other cells are rect_screen_fill's.  use = false: the verdict
+// (not under force) or the lists' bail-out sends the block to every item.
+// Synchronises the stream.
+uint32_t rect_screen_block_rows(drephip_ctx *ctx, uint32_t N, uint32_t R);
+int rect_screen_block(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, const uint64_t *d_rh,
+                      const uint32_t *d_rn, uint32_t N, uint32_t b0, uint32_t b1, uint32_t R, uint32_t C, bool force,
+                      hipStream_t st, ScreenResult *res);
+int rect_screen_fill(drephip_ctx *ctx, const uint32_t *d_qn, const uint32_t *d_rn, uint32_t N, uint32_t b0,
+                     uint32_t b1, uint16_t *d_common, uint16_t *d_denom, hipStream_t st);
 
 constexpr uint32_t kListCols = 512;             // screened columns per whole-row LIST item
 

@@ -987,31 +987,6 @@ __global__ __launch_bounds__(kScWG) void k_screen_denoms(const uint32_t *__restr
     }
 }
 
-// DREPHIP_SCREEN_PROF=1: HIP events between the phases, printed to stderr
-struct ScreenProf {
-    bool on = getenv("DREPHIP_SCREEN_PROF") != nullptr;
-    std::vector<std::pair<const char *, hipEvent_t>> ev;
-    void mark(const char *name, hipStream_t st) {
-        if (!on) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, st);
-        ev.push_back({name, e});
-    }
-    ~ScreenProf() {
-        if (!on || ev.empty()) return;
-        (void)hipEventSynchronize(ev.back().second);
-        fprintf(stderr, "[drephip] screen phases (ms):");
-        for (size_t i = 1; i < ev.size(); i++) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ev[i - 1].second, ev[i].second);
-            fprintf(stderr, " %s %.3f", ev[i].first, ms);
-        }
-        fprintf(stderr, "\n");
-        for (auto &p : ev) (void)hipEventDestroy(p.second);
-    }
-};
-
 // workgroups of kScWG threads for n elements: at least one, at most cap
 static inline uint32_t grid_for(uint64_t n, uint32_t cap) {
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cap, (n + kScWG - 1) / kScWG));
@@ -1199,9 +1174,9 @@ static int screen_pair_map(drephip_ctx *ctx, uint64_t n, hipStream_t st, uint64_
 }
 
 // marked cells (d_bl) -> each row tile's column list and the LIST items
-static int screen_lists(drephip_ctx *ctx, const uint32_t *d_bl, uint32_t ntiles, uint32_t NW, uint32_t C,
-                        uint32_t row0, uint32_t R, const unsigned long long *d_nsimple, hipStream_t st,
-                        ScreenProf &prof, ScreenResult *res) {
+int screen_lists(drephip_ctx *ctx, const uint32_t *d_bl, uint32_t ntiles, uint32_t NW, uint32_t C,
+                 uint32_t row0, uint32_t R, const unsigned long long *d_nsimple, hipStream_t st,
+                 ScreenProf &prof, ScreenResult *res) {
     int rc;
     uint32_t *d_cnt, *d_itc;
     uint64_t *d_coff, *d_cnt64, *h_tot;

@@ -492,8 +492,9 @@ int drephip_last_sparse_stats(drephip_ctx *ctx, uint32_t *blocks, uint64_t *dire
  * by k_rect_merge when a band table cannot be built; k_rect_merge (the
  * literal merge, one lane per pair) for DREPHIP_AP_MERGE and, above 2048, for
  * DREPHIP_RECT_BAND_OFF (drephip_set_rect_band below).  A context set to
- * DREPHIP_AP_BAND, the triangle's selector, gets DREPHIP_ERR_UNSUPPORTED.  No
- * shared-hash screen runs.  Blocking, on the caller's stream; a pending
+ * DREPHIP_AP_BAND, the triangle's selector, gets DREPHIP_ERR_UNSUPPORTED.  The
+ * two-set shared-hash screen (drephip_set_rect_screen below) may run in front
+ * of the table and band kernels, never in front of k_rect_merge.  Blocking, on the caller's stream; a pending
  * drephip_allpairs_device_async on the context is waited for first.
  * drephip_last_kernel_ms `which` 2 / 3 report the rectangle's kernel (the
  * rerun included) and its table build.  With DREPHIP_DEBUG set the band route
@@ -520,6 +521,46 @@ int drephip_set_rect_band(drephip_ctx *ctx, int mode, uint32_t band_cap /* 1..10
  * could not be built and the call's (or a row block's) rows were rerun by
  * k_rect_merge.  Either pointer may be NULL. */
 int drephip_last_rect_info(drephip_ctx *ctx, int *kernel, int *fallback);
+/* The rectangle's two-set shared-hash screen (every drephip_dist_rect* form in
+ * front of the table and band kernels; k_rect_merge -- DREPHIP_AP_MERGE,
+ * drephip_dist_rect_merge_device, DREPHIP_RECT_BAND_OFF above s = 2048 -- is
+ * never screened).  Per block of query rows the block's valid query entries
+ * are sorted by hash, the reference matrix is streamed once past them, and the
+ * (row tile, reference) cells that hold an equal valid hash are marked; the
+ * kernels run on the marked cells only (their RECT, LIST flavours) and every
+ * other cell is common 0, denom min(s, nq + nr).  Exact: the outputs equal the
+ * unscreened call's bit for bit.  Under AUTO a block is screened only when a
+ * count pass over every reference finds checks * ratio <= rows * N * s (checks:
+ * the marking's bit tests; ratio 16, DREPHIP_SCREEN_RATIO), else it runs every
+ * item as without the screen.  A new context takes the mode from the
+ * environment variable DREPHIP_RECT_SCREEN (auto | off | force), read at
+ * creation.  DREPHIP_RECT_SCREEN_MIN_N / _MIN_Q (read per call) lower AUTO's
+ * floors and DREPHIP_RECT_SCREEN_BLOCK_ROWS the rows per block, for tests.
+ * With DREPHIP_DEBUG set, one line per screened block goes to stderr:
+ * "[drephip] rect screen plan: R .. C .. tiles .. marked .. items .. slots ..
+ * pieces .." (row tiles of the block, marked cells, LIST items, item slots
+ * with the idle ones, kernel dispatches; nothing is dispatched at 0 slots);
+ * an unscreened block prints the "rect plan:" / "rect band plan:" line. */
+#define DREPHIP_RECT_SCREEN_AUTO  0  /* from 4096 references and 2048 query rows of a call on (the default) */
+#define DREPHIP_RECT_SCREEN_OFF   1  /* every (row tile, column tile) item runs */
+#define DREPHIP_RECT_SCREEN_FORCE 2  /* every call of any size, no verdict */
+int drephip_set_rect_screen(drephip_ctx *ctx, int mode);
+/* The screen of the last rectangle call (zeros when it did not run): *used = 1
+ * when at least one block ran on its marked cells only; the blocks it looked
+ * at; the query entries sorted and their distinct hashes (summed over blocks);
+ * the count pass's checks (0 under FORCE, which skips it); the marked cells of
+ * the screened blocks; the blocks the verdict sent to the unscreened plan.
+ * Any pointer may be NULL.  drephip_last_rect_info keeps its meaning: the
+ * kernel that computed the cells. */
+int drephip_last_rect_screen_stats(drephip_ctx *ctx, int *used, uint32_t *blocks, uint64_t *query_entries,
+                                   uint64_t *distinct, uint64_t *checks, uint64_t *marked, uint32_t *dense_blocks);
+/* The screen's phases of the last rectangle call in milliseconds, summed over
+ * blocks: sort (keys, radix sort, run heads), count pass, marking, lists, fill.
+ * Measured only while bit 4 of drephip_set_timing is set (else zeros). */
+int drephip_last_rect_screen_ms(drephip_ctx *ctx, double ms[5]);
+/* DREPHIP_RECT_SCREEN's parser: "auto", "off" or "force" -> *mode (anything
+ * else reads as auto, as at context creation).  Needs no device. */
+int drephip_rect_screen_mode_of(const char *text, int *mode);
 /* The same rectangle by k_rect_merge whatever s and whatever the band mode
  * (`mash dist <reference.msh> <query.msh>` by Mash's own loop): the
  * independent cross-check. */

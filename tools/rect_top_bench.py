@@ -76,6 +76,7 @@ def main():
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev).cuda_stream
     ctx = _lib.Context(device=0, k=21, s=s, seed=42)
+    ctx.set_rect_screen(ctx.RECT_SCREEN_OFF)                  # this record is of the unscreened kernels
     res = {"build_id": _lib.lib().drephip_build_id().decode(), "device": torch.cuda.get_device_name(0),
            "queries": Q, "references": N, "sketch": s, "genome_bp": L, "family_size": a.fam, "seed": seed,
            "repeats": a.repeats}
