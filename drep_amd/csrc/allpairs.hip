@@ -1434,6 +1434,22 @@ struct ItemPlan {
     uint64_t gmax = 0;                           // the largest group (plan_rect_items; DREPHIP_DEBUG)
 };
 
+// the per-XCD lists of a plan, one after the other
+static ItemPlan join_lists(const std::vector<std::vector<ItemGroup>> &lists, const uint64_t (&len)[kXcds],
+                           uint64_t gmax) {
+    ItemPlan p;
+    uint64_t lmax = 0;
+    for (uint32_t x = 0; x < kXcds; x++) {
+        p.xs.v[x] = (uint32_t)p.groups.size();
+        p.groups.insert(p.groups.end(), lists[x].begin(), lists[x].end());
+        lmax = std::max(lmax, len[x]);
+    }
+    p.xs.v[kXcds] = (uint32_t)p.groups.size();
+    p.slots = lmax * kXcds;
+    p.gmax = gmax;
+    return p;
+}
+
 static ItemPlan plan_items(uint32_t row0, uint32_t row1, uint32_t N, uint32_t R, uint32_t C) {
     const uint32_t nct = (N + C - 1) / C;
     auto count = [&](uint32_t ct) -> uint64_t {   // row tiles i0 in [row0, row1) with (i0 + 1) / C <= ct
@@ -1460,16 +1476,7 @@ static ItemPlan plan_items(uint32_t row0, uint32_t row1, uint32_t N, uint32_t R,
         lists[best].push_back({(uint32_t)(row0 + g.first * R), g.ct * C, (uint32_t)len[best], (uint32_t)g.size});
         len[best] += g.size;
     }
-    ItemPlan p;
-    uint64_t lmax = 0;
-    for (uint32_t x = 0; x < kXcds; x++) {
-        p.xs.v[x] = (uint32_t)p.groups.size();
-        p.groups.insert(p.groups.end(), lists[x].begin(), lists[x].end());
-        lmax = std::max(lmax, len[x]);
-    }
-    p.xs.v[kXcds] = (uint32_t)p.groups.size();
-    p.slots = lmax * kXcds;
-    return p;
+    return join_lists(lists, len, 0);
 }
 
 // slot t = the (t / 8)-th item of XCD (t % 8)'s list, or idle past its end;
@@ -1573,49 +1580,39 @@ __global__ __launch_bounds__(1024) void k_band_ends(const uint64_t *__restrict__
 constexpr uint64_t kBandChunk = 16384;
 static_assert(kBandChunk % 8 == 0, "chunks keep the XCD-interleaved item order");
 
-// One band-kernel geometry: R rows per tile, 2^BB slots per choice, CAP
-// elements per row per band, MINW = 8 (two workgroups per CU) or 4 (one).
-// scr: the screened lists (LIST kernel over them, every other pair filled as
-// no-shared-hash), or null for the dense item plan.  Value rounds: ~`per`
-// elements per row per round (ctx->band_round, DREPHIP_BAND_ROUND; 0 = one
-// launch per item as before round 5).
-template <int R, int BB, int CAP, int MINW>
-static int launch_band_cfg(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
-                           uint32_t row0, uint32_t row1, uint64_t seg0, uint64_t npairs, uint16_t *d_common,
-                           uint16_t *d_denom, hipStream_t st, const ScreenResult *scr) {
-    const uint32_t cap = std::min(std::max(ctx->band_cap, 1u), (uint32_t)CAP);
-    uint32_t per = ctx->band_round;
-    if (const char *e = getenv("DREPHIP_BAND_ROUND")) per = (uint32_t)atoi(e);
-    const uint32_t nr = per ? (ctx->s + per - 1) / per : 1;
-    uint2 *d_items = nullptr;
-    uint64_t nitems;
-    uint32_t *d_nfail;
+// The band kernel's dispatch at one geometry -- R rows per tile, 2^BB slots
+// per choice, CAP elements per row per band, MINW = 8 (two workgroups per CU)
+// or 4 (one) -- for the triangle (launch_band_cfg) and the rectangle
+// (launch_rect_band): the failure counter, the launches of `nitems` items cut
+// at max_blocks per dispatch, and the counter read back, which synchronises
+// the stream.  LIST: `litems` / `clist` are the screened lists, else `items`
+// the plan's.  *nfail > 0: a band table could not be built with any field
+// pair and the caller reruns its rows by the exact merge kernel.
+// The triangle alone (!RECT) has value rounds -- nr > 1: ~s / nr elements per
+// row per round, the ROUNDS kernel over chunks of kBandChunk items (tests:
+// DREPHIP_BAND_CHUNK) with their states parked in apb_state -- and the
+// per-phase clock sums of DREPHIP_BAND_PROF.
+template <int R, int BB, int CAP, int MINW, bool LIST, bool RECT>
+static int band_dispatch(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N, uint32_t row1,
+                         uint32_t cap, uint64_t seg0, const uint2 *items, const uint4 *litems, const uint32_t *clist,
+                         uint64_t nitems, uint32_t nr, const RectCols &cols, uint16_t *d_common, uint16_t *d_denom,
+                         hipStream_t st, uint32_t *nfail) {
     int rc;
-    std::vector<ItemGroup> groups;                   // lives until the stream sync below
-    if (scr) {
-        nitems = scr->nitems;
-    } else if ((rc = expand_items<false>(ctx, plan_items(row0, row1, N, R, kBandCols), groups, "apb_items", R,
-                                         kBandCols, st, (void **)&d_items, &nitems))) {
-        return rc;
-    }
-    if (nitems == 0) {                              // (screened: the screen wrote the whole segment)
-        if (scr) HIPC(hipStreamSynchronize(st));
-        return DREPHIP_OK;
-    }
+    uint32_t *d_nfail;
     if ((rc = scratch(ctx, "ap_nfail_band", 4, (void **)&d_nfail))) return rc;
     HIPC(hipMemsetAsync(d_nfail, 0, 4, st));
     uint64_t *d_prof = nullptr;                      // DREPHIP_BAND_PROF=1: per-phase wall-clock sums
-    const bool prof = getenv("DREPHIP_BAND_PROF") != nullptr;
+    const bool prof = !RECT && getenv("DREPHIP_BAND_PROF") != nullptr;
     if (prof) {
         if ((rc = scratch(ctx, "apb_prof", 64, (void **)&d_prof))) return rc;
         HIPC(hipMemsetAsync(d_prof, 0, 64, st));
     }
     constexpr size_t lds = band_lds_bytes<R, BB, CAP>();
-    const bool rounds = nr > 1;
-    auto kern = scr ? (rounds ? k_allpairs_band<R, BB, CAP, 1024, MINW, true, true>
-                              : k_allpairs_band<R, BB, CAP, 1024, MINW, true, false>)
-                    : (rounds ? k_allpairs_band<R, BB, CAP, 1024, MINW, false, true>
-                              : k_allpairs_band<R, BB, CAP, 1024, MINW, false, false>);
+    const bool rounds = !RECT && nr > 1;
+    auto kern = k_allpairs_band<R, BB, CAP, 1024, MINW, LIST, false, RECT>;
+    if constexpr (!RECT) {
+        if (rounds) kern = k_allpairs_band<R, BB, CAP, 1024, MINW, LIST, true, false>;
+    }
     HIPC(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     uint32_t *d_state = nullptr;
     uint64_t *d_ends = nullptr;
@@ -1633,18 +1630,17 @@ static int launch_band_cfg(drephip_ctx *ctx, const uint64_t *d_hashes, const uin
         if (rounds && atoll(e) > 0) chunk = std::min<uint64_t>(kBandChunk, std::max<uint64_t>(8, atoll(e) / 8 * 8));
     for (uint64_t b0 = 0; b0 < nitems; b0 += chunk) {
         const uint64_t b1 = std::min(nitems, b0 + chunk);
-        for (uint32_t k = 0; k < nr; k++)
+        for (uint32_t k = 0; k < (rounds ? nr : 1u); k++)
             for (uint64_t i0 = b0; i0 < b1; i0 += max_blocks(1024))
                 hipLaunchKernelGGL(kern, dim3((uint32_t)std::min<uint64_t>(b1 - i0, max_blocks(1024))), dim3(1024), lds,
-                                   st, d_hashes, d_nhash, ctx->s, N, row1, cap, scr ? nullptr : d_items + i0, d_common,
-                                   d_denom, seg0, d_nfail, d_prof, scr ? scr->items + i0 : nullptr,
-                                   scr ? scr->clist : nullptr, rounds ? d_state + (i0 - b0) * band_state_words<R>() : nullptr,
-                                   d_ends, k, RectCols{});
+                                   st, d_hashes, d_nhash, ctx->s, N, row1, cap, LIST ? nullptr : items + i0, d_common,
+                                   d_denom, seg0, d_nfail, d_prof, LIST ? litems + i0 : nullptr, LIST ? clist : nullptr,
+                                   rounds ? d_state + (i0 - b0) * band_state_words<R>() : nullptr, d_ends, k, cols);
     }
     timing_mark(ctx, 2, st, false);
     HIPC(hipGetLastError());
-    uint32_t nfail = 0;
-    HIPC(hipMemcpyAsync(&nfail, d_nfail, 4, hipMemcpyDeviceToHost, st));
+    *nfail = 0;
+    HIPC(hipMemcpyAsync(nfail, d_nfail, 4, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     if (prof) {
         uint64_t h[3];
@@ -1653,6 +1649,46 @@ static int launch_band_cfg(drephip_ctx *ctx, const uint64_t *d_hashes, const uin
                 R, BB, cap, (unsigned long long)h[2], (size_t)nitems, h[2] ? h[0] / 100.0 / h[2] : 0.0,
                 h[2] ? h[1] / 100.0 / h[2] : 0.0);
     }
+    return DREPHIP_OK;
+}
+
+// The triangle at one band geometry.  scr: the screened lists (LIST kernel
+// over them, every other pair filled as no-shared-hash), or null for the dense
+// item plan.  Value rounds: ~`per` elements per row per round (ctx->band_round,
+// DREPHIP_BAND_ROUND; 0 = one launch per item as before round 5).
+template <int R, int BB, int CAP, int MINW>
+static int launch_band_cfg(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t N,
+                           uint32_t row0, uint32_t row1, uint64_t seg0, uint64_t npairs, uint16_t *d_common,
+                           uint16_t *d_denom, hipStream_t st, const ScreenResult *scr) {
+    const uint32_t cap = std::min(std::max(ctx->band_cap, 1u), (uint32_t)CAP);
+    // (DREPHIP_BAND_ROUND here, DREPHIP_BAND_PROF and DREPHIP_BAND_CHUNK in
+    // band_dispatch: the triangle's only -- the rectangle has no value rounds)
+    uint32_t per = ctx->band_round;
+    if (const char *e = getenv("DREPHIP_BAND_ROUND")) per = (uint32_t)atoi(e);
+    const uint32_t nr = per ? (ctx->s + per - 1) / per : 1;
+    uint2 *d_items = nullptr;
+    uint64_t nitems;
+    int rc;
+    std::vector<ItemGroup> groups;                   // lives until band_dispatch's stream sync
+    if (scr) {
+        nitems = scr->nitems;
+    } else if ((rc = expand_items<false>(ctx, plan_items(row0, row1, N, R, kBandCols), groups, "apb_items", R,
+                                         kBandCols, st, (void **)&d_items, &nitems))) {
+        return rc;
+    }
+    if (nitems == 0) {
+        // screened: the screen wrote the whole segment, and the call still
+        // synchronises (the rectangle's screened path returns without: its
+        // callers synchronise per block)
+        if (scr) HIPC(hipStreamSynchronize(st));
+        return DREPHIP_OK;
+    }
+    uint32_t nfail;
+    rc = scr ? band_dispatch<R, BB, CAP, MINW, true, false>(ctx, d_hashes, d_nhash, N, row1, cap, seg0, nullptr, scr->items,
+                                                            scr->clist, nitems, nr, RectCols{}, d_common, d_denom, st, &nfail)
+             : band_dispatch<R, BB, CAP, MINW, false, false>(ctx, d_hashes, d_nhash, N, row1, cap, seg0, d_items, nullptr,
+                                                             nullptr, nitems, nr, RectCols{}, d_common, d_denom, st, &nfail);
+    if (rc) return rc;
     if (nfail)   // a band table could not be built with any field pair: exact merge kernel instead
         return launch_merge(ctx, d_hashes, d_nhash, N, seg0, npairs, d_common, d_denom, st);
     return DREPHIP_OK;
@@ -1679,14 +1715,116 @@ static int launch_band(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_
                                                st, scr);
 }
 
-// LIST: the screened items / column list (clist)
-template <int R, int NCH, int MINW, bool LIST, bool SPARSE = false>
-static int launch_q(drephip_ctx *ctx, uint32_t nitems, size_t lds, hipStream_t st, const uint64_t *h,
-                    const uint32_t *nh, const uint32_t *blk, uint32_t stride, const uint8_t *fam, uint32_t N, uint32_t row0,
-                    uint32_t row1, uint32_t B, const uint4 *items, uint16_t *cm, uint16_t *dn,
-                    uint64_t seg0, const uint32_t *clist, const uint32_t *cmask, SparseOut sp = SparseOut{}) {
-    HIPC(hipFuncSetAttribute((const void *)k_allpairs_q<R, NCH, MINW, LIST, SPARSE>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+// ------------------------------------------------------- whole-row geometry
+// What (s, R) fix for the whole-row kernel: B-bit fields with H = 2^B >= 2s
+// (load <= 1/4, and every position and the empty word's 2^B - 1 fit the
+// field; 32-bit families need B <= 12), TS = 2H slot words per row, the
+// `bytes` of the row group's image (slot words + high words), its `stride` in
+// words (a 16-byte multiple) = the kernel's `lds` bytes of dynamic LDS, the
+// kernel's chunk class nch (8: s <= 512, 16: s <= 1024, else 32) and its
+// launch bound minw: 8 = two workgroups per CU up to 80 KiB of LDS, else 4.
+struct QGeom {
+    uint32_t B, TS, stride;
+    size_t bytes, lds;
+    int nch, minw;
+};
+constexpr QGeom q_geom(uint32_t s, uint32_t R) {
+    uint32_t B = 4;
+    while ((1u << B) < 2 * s) B++;
+    const uint32_t TS = 2u << B;
+    const size_t bytes = q_lds_bytes(R, TS, s);
+    const uint32_t stride = (uint32_t)((bytes / 4 + 3) & ~3ull);
+    const size_t lds = (size_t)stride * 4;
+    const uint32_t chunks = (s + 63) / 64;
+    return {B, TS, stride, bytes, lds, chunks <= 8 ? 8 : chunks <= 16 ? 16 : 32, lds <= 80 * 1024 ? 8 : 4};
+}
+// rows per workgroup: the most (8, 4, 2, 1) whose tables + high words fit
+constexpr uint32_t kQRowChoices[] = {8, 4, 2, 1};
+constexpr uint32_t q_auto_rows(uint32_t s) {
+    for (uint32_t r : kQRowChoices)
+        if (q_geom(s, r).bytes + 16 <= kLdsBudget) return r;
+    return 1;
+}
+// A/B override (DREPHIP_AP_R): r rows per workgroup if their tables fit the
+// whole 160 KiB of a CU (one workgroup per CU above 80 KiB)
+constexpr bool q_override_admits(uint32_t s, uint32_t r) {
+    return (r == 1 || r == 2 || r == 4 || r == 8) && q_geom(s, r).bytes <= 160 * 1024;
+}
+
+// The geometries k_allpairs_q is instantiated at.  MINW follows from (R, NCH):
+// lds = 4 R (TS + s) with TS fixed by s and NCH fixing the range of s, proved
+// below for every s the kernel takes.  rect_list: the rectangle's screened
+// (RECT, LIST) flavours exist -- at the geometries allpairs_geometry picks by
+// itself for some s <= 2048; an A/B override of R outside them keeps the
+// unscreened plan (rect_list_geometry).
+struct QRow { int R, NCH, MINW; bool rect_list; };
+constexpr QRow kQRows[] = {
+    {8, 8, 8, true},  {4, 8, 8, false},  {2, 8, 8, false},  {1, 8, 8, false},
+    {8, 16, 4, true}, {4, 16, 8, true},  {2, 16, 8, false}, {1, 16, 8, false},
+    {4, 32, 4, true}, {2, 32, 8, true},  {1, 32, 8, false},
+};
+constexpr int kNQRows = (int)(sizeof(kQRows) / sizeof(kQRows[0]));
+constexpr int q_row(uint32_t R, int nch) {           // index into kQRows, or -1
+    for (int i = 0; i < kNQRows; i++)
+        if ((uint32_t)kQRows[i].R == R && kQRows[i].NCH == nch) return i;
+    return -1;
+}
+// every (s, R) allpairs_geometry can return on the table path -- its own
+// choice and every DREPHIP_AP_R it admits -- has a row, and the row's MINW is
+// the one its image size asks for
+constexpr bool q_rows_hold(uint32_t s0, uint32_t s1) {
+    for (uint32_t s = s0; s <= s1; s++)
+        for (uint32_t r : kQRowChoices) {
+            if (r != q_auto_rows(s) && !q_override_admits(s, r)) continue;
+            const QGeom g = q_geom(s, r);
+            const int i = q_row(r, g.nch);
+            if (i < 0 || kQRows[i].MINW != g.minw) return false;
+        }
+    return true;
+}
+static_assert(q_rows_hold(1, 512), "whole-row geometries, 8 chunks");
+static_assert(q_rows_hold(513, 1024), "whole-row geometries, 16 chunks");
+static_assert(q_rows_hold(1025, 1536) && q_rows_hold(1537, 2048), "whole-row geometries, 32 chunks");
+static_assert(q_geom(2048, 1).B == 12 && q_geom(2049, 1).B == 13, "s <= 2048 is the whole-row path");
+
+// Calls f(QTag<i>{}) for the row i of kQRows that (R, g.nch) names.  A
+// combination without a row is an error (nothing falls through to another
+// geometry's kernel), and so is an image whose size disagrees with the row's
+// MINW: the other kernel is not instantiated.
+template <int I>
+struct QTag {
+    static constexpr int R = kQRows[I].R, NCH = kQRows[I].NCH, MINW = kQRows[I].MINW;
+    static constexpr bool rect_list = kQRows[I].rect_list;
+};
+template <int I = 0, class F>
+static int q_dispatch(uint32_t R, const QGeom &g, F &&f) {
+    if constexpr (I < kNQRows) {
+        if ((uint32_t)kQRows[I].R != R || kQRows[I].NCH != g.nch) return q_dispatch<I + 1>(R, g, f);
+        if (kQRows[I].MINW != g.minw) {
+            set_error("all-pairs: a row image of " + std::to_string(g.lds) + " bytes at R " + std::to_string(R) +
+                      " disagrees with the geometry table's workgroups per CU");
+            return DREPHIP_ERR_UNSUPPORTED;
+        }
+        return f(QTag<I>{});
+    } else {
+        set_error("all-pairs: no kernel at this geometry (R " + std::to_string(R) + ", " + std::to_string(g.nch) +
+                  " chunks)");
+        return DREPHIP_ERR_UNSUPPORTED;
+    }
+}
+
+// The launches of k_allpairs_q<R, NCH, MINW, LIST, SPARSE, RECT> over `nitems`
+// items, cut at max_blocks per dispatch.  LIST: the screened items / column
+// list (clist).  The kernel's trailing arguments are the caller's: the
+// triangle's seg0 and (not LIST) chunk masks, the records' SparseOut, the
+// rectangle's reference matrix.
+template <int R, int NCH, int MINW, bool LIST, bool SPARSE, bool RECT>
+static int launch_q(drephip_ctx *ctx, uint32_t nitems, const QGeom &g, hipStream_t st, const uint64_t *h,
+                    const uint32_t *nh, const uint32_t *blk, const uint8_t *fam, uint32_t N, uint32_t row0,
+                    uint32_t row1, const uint4 *items, uint16_t *cm, uint16_t *dn, uint64_t seg0,
+                    const uint32_t *clist, const uint32_t *cmask, const SparseOut &sp, const RectCols &rc) {
+    HIPC(hipFuncSetAttribute((const void *)k_allpairs_q<R, NCH, MINW, LIST, SPARSE, RECT>,
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
     // the branch-free hit probe and the union-rank end for rows with matches
     // (probe_rows_v, ap_columns HITQ/HITV); DREPHIP_AP_HIT=0 runs the round-5
     // probe and ends (A/B)
@@ -1694,12 +1832,44 @@ static int launch_q(drephip_ctx *ctx, uint32_t nitems, size_t lds, hipStream_t s
     const int hitq = he ? atoi(he) : 1;
     timing_mark(ctx, 2, st, true);
     for (uint32_t i0 = 0; i0 < nitems; i0 += (uint32_t)max_blocks(kApWG))
-        hipLaunchKernelGGL((k_allpairs_q<R, NCH, MINW, LIST, SPARSE>),
-                           dim3(std::min<uint32_t>(nitems - i0, (uint32_t)max_blocks(kApWG))), dim3(kApWG), lds, st, h,
-                           nh, blk, stride, fam, ctx->s, N, row0, row1, B, items + i0, cm, dn, seg0, clist, hitq,
-                           LIST ? nullptr : cmask, sp);
+        hipLaunchKernelGGL((k_allpairs_q<R, NCH, MINW, LIST, SPARSE, RECT>),
+                           dim3(std::min<uint32_t>(nitems - i0, (uint32_t)max_blocks(kApWG))), dim3(kApWG), g.lds, st, h,
+                           nh, blk, g.stride, fam, ctx->s, N, row0, row1, g.B, items + i0, cm, dn, seg0, clist, hitq,
+                           cmask, sp, rc);
     timing_mark(ctx, 2, st, false);
     HIPC(hipGetLastError());
+    return DREPHIP_OK;
+}
+
+// The row-group LDS images (tables + high words) of rows [row0, row1) at R
+// rows per group, built once per call by k_build_q32 into the scratch ap_blk,
+// the rows' family bytes into ap_fam.  Queued on st.
+static int build_row_images(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t *d_nhash, uint32_t row0,
+                            uint32_t row1, uint32_t R, const QGeom &g, hipStream_t st, uint32_t **d_blk,
+                            uint8_t **d_fam) {
+    const uint32_t ngroups = (row1 - row0 + R - 1) / R;
+    int rc;
+    if ((rc = scratch(ctx, "ap_blk", (uint64_t)ngroups * g.stride * 4, (void **)d_blk))) return rc;
+    if ((rc = scratch(ctx, "ap_fam", ((uint64_t)ngroups * R + 7) & ~7ull, (void **)d_fam))) return rc;
+    const size_t blds = (size_t)g.TS * 4;
+    HIPC(hipFuncSetAttribute((const void *)k_build_q32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds));
+    timing_mark(ctx, 3, st, true);
+    hipLaunchKernelGGL(k_build_q32, dim3(ngroups * R), dim3(1024), blds, st, d_hashes, d_nhash, ctx->s, row0, row1, g.B,
+                       R, *d_blk, g.stride, *d_fam);
+    timing_mark(ctx, 3, st, false);
+    HIPC(hipGetLastError());
+    return DREPHIP_OK;
+}
+
+// DREPHIP_DEBUG: a screen's items, read back after a stream sync -- the real
+// ones among the idle slots and the most columns of one
+static int count_screened_items(const ScreenResult &scr, hipStream_t st, uint64_t *items, uint64_t *cmax) {
+    std::vector<uint4> h(scr.nitems);
+    HIPC(hipStreamSynchronize(st));
+    if (scr.nitems) HIPC(hipMemcpy(h.data(), scr.items, scr.nitems * sizeof(uint4), hipMemcpyDeviceToHost));
+    *items = *cmax = 0;
+    for (const uint4 &it : h)
+        if (it.x != kIdleItem) { (*items)++; *cmax = std::max<uint64_t>(*cmax, it.z); }
     return DREPHIP_OK;
 }
 
@@ -1719,31 +1889,22 @@ bool screen_applies(drephip_ctx *ctx, uint32_t N) {
 }
 
 // Rows per work item / row tile and the kernel path for this context's s:
-// whole-row LDS tables (B-bit fields, 2H slots, H = 2^B >= 2s) when they fit,
-// else value bands.  The sharded screen's parts tile rows by the same R.
+// whole-row LDS tables (QGeom) when they fit, else value bands.  The sharded
+// screen's parts tile rows by the same R.
 int allpairs_geometry(drephip_ctx *ctx, uint32_t *R_out, int *path_out) {
     const uint32_t s = ctx->s;
-    // table: 2H slots, H = 2^B >= 2s (load <= 1/4, and every position and the
-    // empty word's 2^B - 1 fit the field); 32-bit families need B <= 12
-    uint32_t B = 4;
-    while ((1u << B) < 2 * s) B++;
-    const uint32_t TS = 2u << B;
-    const bool fits = B <= 12 && q_lds_bytes(1, TS, s) <= kLdsBudget;
+    const QGeom g1 = q_geom(s, 1);
+    const bool fits = g1.B <= 12 && g1.bytes <= kLdsBudget;
     int path = ctx->ap_path;
     if (path == DREPHIP_AP_AUTO) path = fits ? DREPHIP_AP_TABLE : DREPHIP_AP_BAND;
     if (path == DREPHIP_AP_TABLE && !fits) {
         set_error("whole-row table all-pairs kernel needs s <= 2048");
         return DREPHIP_ERR_UNSUPPORTED;
     }
-    // rows per workgroup: the most (8, 4, 2, 1) whose tables + high words fit
-    static const uint32_t kR[] = {8, 4, 2, 1};
-    uint32_t R = 1;
-    for (uint32_t r : kR) if (q_lds_bytes(r, TS, s) + 16 <= kLdsBudget) { R = r; break; }
+    uint32_t R = q_auto_rows(s);
     if (const char *e = getenv("DREPHIP_AP_R")) {
-        // A/B override: R rows per workgroup if their tables fit the whole
-        // 160 KiB of a CU (one workgroup per CU above 80 KiB)
         const uint32_t r = (uint32_t)atoi(e);
-        if ((r == 1 || r == 2 || r == 4 || r == 8) && q_lds_bytes(r, TS, s) <= 160 * 1024) R = r;
+        if (q_override_admits(s, r)) R = r;
     }
     if (path == DREPHIP_AP_BAND) R = kBandR;
     *R_out = R;
@@ -1772,9 +1933,6 @@ int allpairs_device_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
     const int rc0 = allpairs_geometry(ctx, &R, &path);
     if (force_merge) path = DREPHIP_AP_MERGE;         // (the literal merge needs no table)
     else if (rc0) return rc0;
-    uint32_t B = 4;
-    while ((1u << B) < 2 * s) B++;
-    const uint32_t TS = 2u << B;
     ctx->last_screen = ScreenResult{};
     if (path == DREPHIP_AP_MERGE)
         return launch_merge(ctx, d_hashes, d_nhash, N, seg0, npairs, d_common, d_denom, st);
@@ -1806,22 +1964,12 @@ int allpairs_device_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
                            scr.use ? &scr : nullptr);
 
     // row-group LDS images (tables + high words), built once per call
-    const uint32_t nrows = row1 - row0;
-    const uint32_t ngroups = (nrows + R - 1) / R;
-    const uint32_t stride = (uint32_t)((q_lds_bytes(R, TS, s) / 4 + 3) & ~3ull);   // words, 16-B multiple
+    const QGeom g = q_geom(s, R);
     uint32_t *d_blk;
     uint8_t *d_fam;
     uint4 *d_items;
     int rc;
-    if ((rc = scratch(ctx, "ap_blk", (uint64_t)ngroups * stride * 4, (void **)&d_blk))) return rc;
-    if ((rc = scratch(ctx, "ap_fam", ((uint64_t)ngroups * R + 7) & ~7ull, (void **)&d_fam))) return rc;
-    const size_t blds = (size_t)TS * 4;
-    HIPC(hipFuncSetAttribute((const void *)k_build_q32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds));
-    timing_mark(ctx, 3, st, true);
-    hipLaunchKernelGGL(k_build_q32, dim3(ngroups * R), dim3(1024), blds, st, d_hashes, d_nhash, s, row0, row1, B, R,
-                       d_blk, stride, d_fam);
-    timing_mark(ctx, 3, st, false);
-    HIPC(hipGetLastError());
+    if ((rc = build_row_images(ctx, d_hashes, d_nhash, row0, row1, R, g, st, &d_blk, &d_fam))) return rc;
     // column tile: the widest (<= kApCols) whose item count still gives every
     // workgroup slot of the chip (256 CUs x 2) about four items; small
     // problems (a rank's shard on 8 GPUs, N ~ 10^3) get narrower items.  (Items
@@ -1846,13 +1994,8 @@ int allpairs_device_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
         const bool cached = !scr.use && ctx->ap_items_gen == ctx->alloc_gen && !memcmp(ctx->ap_items_key, key, sizeof(key));
         uint64_t items = nitems_for(C), slots = cached ? ctx->ap_items_n : 0, cmax = std::min(C, N);
         if (scr.use) {
-            std::vector<uint4> h(scr.nitems);
-            HIPC(hipStreamSynchronize(st));
-            if (scr.nitems) HIPC(hipMemcpy(h.data(), scr.items, scr.nitems * sizeof(uint4), hipMemcpyDeviceToHost));
-            items = cmax = 0;
+            if ((rc = count_screened_items(scr, st, &items, &cmax))) return rc;
             slots = scr.nitems;
-            for (const uint4 &it : h)
-                if (it.x != kIdleItem) { items++; cmax = std::max<uint64_t>(cmax, it.z); }
         } else if (!cached) {
             slots = plan_items(row0, row1, N, R, C).slots;
         }
@@ -1879,37 +2022,15 @@ int allpairs_device_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
     const bool lst = scr.use;
     // a row whose table cannot be built is merged literally inside the main
     // kernel (k_allpairs_q): no host round trip, nothing to check afterwards
-    const size_t lds = (size_t)stride * 4;
-    const uint32_t nch = (s + 63) / 64;
-    // two workgroups per CU when the LDS allows
-    const bool two = lds <= 80 * 1024;
-#define DREPHIP_Q1(RR, NC, MW, LS) launch_q<RR, NC, MW, LS>(ctx, ni, lds, st, d_hashes, d_nhash, d_blk, stride, d_fam, N, row0, row1, B, \
-                                                          d_items, d_common, d_denom, seg0, scr.clist, scr.use ? nullptr : scr.cmask)
-#define DREPHIP_Q(RR, NC) (two ? (lst ? DREPHIP_Q1(RR, NC, 8, true) : DREPHIP_Q1(RR, NC, 8, false)) \
-                               : (lst ? DREPHIP_Q1(RR, NC, 4, true) : DREPHIP_Q1(RR, NC, 4, false)))
-    if (nch <= 8) {
-        switch (R) {
-            case 8: rc = DREPHIP_Q(8, 8); break;
-            case 4: rc = DREPHIP_Q(4, 8); break;
-            case 2: rc = DREPHIP_Q(2, 8); break;
-            default: rc = DREPHIP_Q(1, 8); break;
-        }
-    } else if (nch <= 16) {
-        switch (R) {
-            case 8: rc = DREPHIP_Q(8, 16); break;
-            case 4: rc = DREPHIP_Q(4, 16); break;
-            case 2: rc = DREPHIP_Q(2, 16); break;
-            default: rc = DREPHIP_Q(1, 16); break;
-        }
-    } else {
-        switch (R) {
-            case 4: rc = DREPHIP_Q(4, 32); break;
-            case 2: rc = DREPHIP_Q(2, 32); break;
-            default: rc = DREPHIP_Q(1, 32); break;
-        }
-    }
-#undef DREPHIP_Q
-#undef DREPHIP_Q1
+    rc = q_dispatch(R, g, [&](auto t) {
+        using T = decltype(t);
+        auto run = [&](auto list) {
+            return launch_q<T::R, T::NCH, T::MINW, decltype(list)::value, false, false>(
+                ctx, ni, g, st, d_hashes, d_nhash, d_blk, d_fam, N, row0, row1, d_items, d_common, d_denom, seg0,
+                scr.clist, lst ? nullptr : scr.cmask, SparseOut{}, RectCols{});
+        };
+        return lst ? run(std::true_type{}) : run(std::false_type{});
+    });
     if (rc) return rc;
     if (defer) {
         // drephip_allpairs_wait (or the next all-pairs call) waits for this event
@@ -1926,9 +2047,7 @@ int allpairs_device_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
 // ------------------------------------------------------- sparse LIST launch
 // bytes of row-group image (slot words + high words) per row at R rows per tile
 uint64_t allpairs_image_bytes_per_row(drephip_ctx *ctx, uint32_t R) {
-    uint32_t B = 4;
-    while ((1u << B) < 2 * ctx->s) B++;
-    return (q_lds_bytes(R, 2u << B, ctx->s) + 15) / R;
+    return (q_geom(ctx->s, R).bytes + 15) / R;
 }
 
 // The screened items of rows [row0, row1) through the whole-row LIST kernel in
@@ -1938,54 +2057,17 @@ int allpairs_sparse_list_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const 
                               uint32_t row0, uint32_t row1, uint32_t R, const ScreenResult &scr,
                               const SparseOut &out, hipStream_t st) {
     if (!scr.use || scr.nitems == 0) return DREPHIP_OK;
-    const uint32_t s = ctx->s;
-    uint32_t B = 4;
-    while ((1u << B) < 2 * s) B++;
-    const uint32_t TS = 2u << B;
-    const uint32_t ngroups = (row1 - row0 + R - 1) / R;
-    const uint32_t stride = (uint32_t)((q_lds_bytes(R, TS, s) / 4 + 3) & ~3ull);
+    const QGeom g = q_geom(ctx->s, R);
     uint32_t *d_blk;
     uint8_t *d_fam;
     int rc;
-    if ((rc = scratch(ctx, "ap_blk", (uint64_t)ngroups * stride * 4, (void **)&d_blk))) return rc;
-    if ((rc = scratch(ctx, "ap_fam", ((uint64_t)ngroups * R + 7) & ~7ull, (void **)&d_fam))) return rc;
-    const size_t blds = (size_t)TS * 4;
-    HIPC(hipFuncSetAttribute((const void *)k_build_q32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds));
-    timing_mark(ctx, 3, st, true);
-    hipLaunchKernelGGL(k_build_q32, dim3(ngroups * R), dim3(1024), blds, st, d_hashes, d_nhash, s, row0, row1, B, R,
-                       d_blk, stride, d_fam);
-    timing_mark(ctx, 3, st, false);
-    HIPC(hipGetLastError());
-    const size_t lds = (size_t)stride * 4;
-    const uint32_t nch = (s + 63) / 64;
-    const bool two = lds <= 80 * 1024;
-#define DREPHIP_QS1(RR, NC, MW) launch_q<RR, NC, MW, true, true>(ctx, scr.nitems, lds, st, d_hashes, d_nhash, d_blk, stride, d_fam, N, \
-                                                                 row0, row1, B, scr.items, nullptr, nullptr, 0, scr.clist, nullptr, out)
-#define DREPHIP_QS(RR, NC) (two ? DREPHIP_QS1(RR, NC, 8) : DREPHIP_QS1(RR, NC, 4))
-    if (nch <= 8) {
-        switch (R) {
-            case 8: rc = DREPHIP_QS(8, 8); break;
-            case 4: rc = DREPHIP_QS(4, 8); break;
-            case 2: rc = DREPHIP_QS(2, 8); break;
-            default: rc = DREPHIP_QS(1, 8); break;
-        }
-    } else if (nch <= 16) {
-        switch (R) {
-            case 8: rc = DREPHIP_QS(8, 16); break;
-            case 4: rc = DREPHIP_QS(4, 16); break;
-            case 2: rc = DREPHIP_QS(2, 16); break;
-            default: rc = DREPHIP_QS(1, 16); break;
-        }
-    } else {
-        switch (R) {
-            case 4: rc = DREPHIP_QS(4, 32); break;
-            case 2: rc = DREPHIP_QS(2, 32); break;
-            default: rc = DREPHIP_QS(1, 32); break;
-        }
-    }
-#undef DREPHIP_QS
-#undef DREPHIP_QS1
-    return rc;
+    if ((rc = build_row_images(ctx, d_hashes, d_nhash, row0, row1, R, g, st, &d_blk, &d_fam))) return rc;
+    return q_dispatch(R, g, [&](auto t) {
+        using T = decltype(t);
+        return launch_q<T::R, T::NCH, T::MINW, true, true, false>(ctx, scr.nitems, g, st, d_hashes, d_nhash, d_blk, d_fam,
+                                                                  N, row0, row1, scr.items, nullptr, nullptr, 0, scr.clist,
+                                                                  nullptr, out, RectCols{});
+    });
 }
 
 // ------------------------------------------------- query against reference
@@ -2168,17 +2250,7 @@ static ItemPlan plan_rect_items(uint32_t q0, uint32_t q1, uint32_t Nc, uint32_t 
                 lists[best].push_back({(uint32_t)(q0 + i * R), ct * C, (uint32_t)len[best], (uint32_t)size});
                 len[best] += size;
             }
-    ItemPlan p;
-    uint64_t lmax = 0;
-    for (uint32_t x = 0; x < kXcds; x++) {
-        p.xs.v[x] = (uint32_t)p.groups.size();
-        p.groups.insert(p.groups.end(), lists[x].begin(), lists[x].end());
-        lmax = std::max(lmax, len[x]);
-    }
-    p.xs.v[kXcds] = (uint32_t)p.groups.size();
-    p.slots = lmax * kXcds;
-    p.gmax = gmax;
-    return p;
+    return join_lists(lists, len, gmax);
 }
 
 // DREPHIP_DEBUG: the geometry a screened block runs at (the tests read it);
@@ -2186,35 +2258,11 @@ static ItemPlan plan_rect_items(uint32_t q0, uint32_t q1, uint32_t Nc, uint32_t 
 static int rect_screen_plan_line(drephip_ctx *ctx, const ScreenResult &scr, uint32_t nrows, uint32_t R, uint32_t C,
                                  uint32_t per, hipStream_t st) {
     if (!getenv("DREPHIP_DEBUG")) return DREPHIP_OK;
-    std::vector<uint4> h(scr.nitems);
-    HIPC(hipStreamSynchronize(st));
-    if (scr.nitems) HIPC(hipMemcpy(h.data(), scr.items, scr.nitems * sizeof(uint4), hipMemcpyDeviceToHost));
-    uint64_t items = 0;
-    for (const uint4 &it : h) items += it.x != kIdleItem;
+    uint64_t items, cmax;
+    if (int rc = count_screened_items(scr, st, &items, &cmax)) return rc;
     fprintf(stderr, "[drephip] rect screen plan: R %u C %u tiles %u marked %llu items %llu slots %u pieces %u\n", R, C,
             (nrows + R - 1) / R, (unsigned long long)scr.marked, (unsigned long long)items, scr.nitems,
             (scr.nitems + per - 1) / per);
-    return DREPHIP_OK;
-}
-
-// LIST: the two-set screen's items / column list (clist)
-template <int R, int NCH, int MINW, bool SPARSE, bool LIST = false>
-static int launch_rect_q(drephip_ctx *ctx, uint32_t nitems, size_t lds, hipStream_t st, const uint64_t *qh,
-                         const uint32_t *qn, const uint32_t *blk, uint32_t stride, const uint8_t *fam, uint32_t Q,
-                         uint32_t q0, uint32_t q1, uint32_t B, const uint4 *items, uint16_t *cm, uint16_t *dn,
-                         const RectCols &rc, const SparseOut &sp, const uint32_t *clist = nullptr) {
-    HIPC(hipFuncSetAttribute((const void *)k_allpairs_q<R, NCH, MINW, LIST, SPARSE, true>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const char *he = getenv("DREPHIP_AP_HIT");         // as launch_q
-    const int hitq = he ? atoi(he) : 1;
-    timing_mark(ctx, 2, st, true);
-    for (uint32_t i0 = 0; i0 < nitems; i0 += (uint32_t)max_blocks(kApWG))
-        hipLaunchKernelGGL((k_allpairs_q<R, NCH, MINW, LIST, SPARSE, true>),
-                           dim3(std::min<uint32_t>(nitems - i0, (uint32_t)max_blocks(kApWG))), dim3(kApWG), lds, st, qh,
-                           qn, blk, stride, fam, ctx->s, Q, q0, q1, B, items + i0, cm, dn, 0ull, clist, hitq, nullptr,
-                           sp, rc);
-    timing_mark(ctx, 2, st, false);
-    HIPC(hipGetLastError());
     return DREPHIP_OK;
 }
 
@@ -2230,108 +2278,69 @@ static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_
                       const ScreenResult *scr = nullptr) {
     if (scr && rect_screen_plan_line(ctx, *scr, q1 - q0, R, kApCols, (uint32_t)max_blocks(kApWG), st)) return DREPHIP_ERR_HIP;
     if (scr && scr->nitems == 0) return DREPHIP_OK;
-    const uint32_t s = ctx->s;
-    uint32_t B = 4;
-    while ((1u << B) < 2 * s) B++;
-    const uint32_t TS = 2u << B;
-    const uint32_t nrows = q1 - q0;
-    const uint32_t ngroups = (nrows + R - 1) / R;
-    const uint32_t stride = (uint32_t)((q_lds_bytes(R, TS, s) / 4 + 3) & ~3ull);   // words, 16-B multiple
+    const QGeom g = q_geom(ctx->s, R);
+    const uint32_t ngroups = (q1 - q0 + R - 1) / R;
     uint32_t *d_blk;
     uint8_t *d_fam;
-    uint4 *d_items;
+    uint4 *d_items = nullptr;
     int rc;
-    if ((rc = scratch(ctx, "ap_blk", (uint64_t)ngroups * stride * 4, (void **)&d_blk))) return rc;
-    if ((rc = scratch(ctx, "ap_fam", ((uint64_t)ngroups * R + 7) & ~7ull, (void **)&d_fam))) return rc;
-    const size_t blds = (size_t)TS * 4;
-    HIPC(hipFuncSetAttribute((const void *)k_build_q32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds));
-    timing_mark(ctx, 3, st, true);
-    hipLaunchKernelGGL(k_build_q32, dim3(ngroups * R), dim3(1024), blds, st, d_qh, d_qn, s, q0, q1, B, R, d_blk, stride,
-                       d_fam);
-    timing_mark(ctx, 3, st, false);
-    HIPC(hipGetLastError());
-    const size_t lds = (size_t)stride * 4;
-    const uint32_t nch = (s + 63) / 64;
-    const bool two = lds <= 80 * 1024;              // two workgroups per CU when the LDS allows
+    if ((rc = build_row_images(ctx, d_qh, d_qn, q0, q1, R, g, st, &d_blk, &d_fam))) return rc;
     const RectCols cols{d_rh, d_rn, N};
     const SparseOut out = sp ? *sp : SparseOut{};
-    if (scr) {
-        // the LIST flavours exist at the geometries allpairs_geometry picks by
-        // itself (rect_list_geometry; the caller has checked)
-        const uint32_t ni = scr->nitems;
-        const uint4 *li = scr->items;
-#define DREPHIP_QL(RR, NC, MW) (sp ? launch_rect_q<RR, NC, MW, true, true>(ctx, ni, lds, st, d_qh, d_qn, d_blk, stride, d_fam, Q, q0, q1, B, \
-                                                                          li, d_common, d_denom, cols, out, scr->clist)      \
-                                   : launch_rect_q<RR, NC, MW, false, true>(ctx, ni, lds, st, d_qh, d_qn, d_blk, stride, d_fam, Q, q0, q1, \
-                                                                           B, li, d_common, d_denom, cols, out, scr->clist))
-        if (R == 8 && nch <= 8 && two) return DREPHIP_QL(8, 8, 8);
-        if (R == 8 && nch > 8 && nch <= 16 && !two) return DREPHIP_QL(8, 16, 4);
-        if (R == 4 && nch > 8 && nch <= 16 && two) return DREPHIP_QL(4, 16, 8);
-        if (R == 4 && nch > 16 && !two) return DREPHIP_QL(4, 32, 4);
-        if (R == 2 && nch > 16 && two) return DREPHIP_QL(2, 32, 8);
-#undef DREPHIP_QL
-        set_error("the screened rectangle has no kernel at this geometry");
-        return DREPHIP_ERR_UNSUPPORTED;
-    }
-    // column tile: the rule of the triangle's plan -- the widest (<= kApCols)
-    // that still gives every workgroup slot of the chip about four items
-    uint32_t C = kApCols;
-    auto nitems_for = [&](uint32_t c) { return (uint64_t)ngroups * ((N + c - 1) / c); };
-    while (C > kApMinCols && nitems_for(C) < 4ull * kApSlots) C /= 2;
-    if (nitems_for(C) + kXcds * 16ull >= (1ull << 32)) {
-        set_error("the rectangle's item list exceeds 2^32 entries: call it in row ranges");
-        return DREPHIP_ERR_UNSUPPORTED;
-    }
-    // the plan is not cached: its key (Q, q0, q1, N, R, C) is not the
-    // triangle's, and planning is a few thousand groups on the host
-    uint64_t ni64;
-    ItemPlan plan = plan_rect_items(q0, q1, N, R, C);
-    const uint64_t gmax = plan.gmax;
-    if ((rc = expand_items<true>(ctx, std::move(plan), groups, "rect_items", R, C, st, (void **)&d_items, &ni64)))
-        return rc;
-    const uint32_t ni = (uint32_t)ni64;
-    if (getenv("DREPHIP_DEBUG")) {                  // the geometry this call runs at (the tests read it)
-        const uint64_t per = max_blocks(kApWG);     // items per k_allpairs_q dispatch (launch_rect_q)
-        fprintf(stderr, "[drephip] rect plan: R %u C %u items %llu slots %llu gmax %llu pieces %u\n", R, C,
-                (unsigned long long)nitems_for(C), (unsigned long long)ni64, (unsigned long long)gmax,
-                (uint32_t)((ni64 + per - 1) / per));
-    }
-#define DREPHIP_QR1(RR, NC, MW, SP) launch_rect_q<RR, NC, MW, SP>(ctx, ni, lds, st, d_qh, d_qn, d_blk, stride, d_fam, Q, q0, q1, B, \
-                                                                  d_items, d_common, d_denom, cols, out)
-#define DREPHIP_QR(RR, NC) (two ? (sp ? DREPHIP_QR1(RR, NC, 8, true) : DREPHIP_QR1(RR, NC, 8, false)) \
-                                : (sp ? DREPHIP_QR1(RR, NC, 4, true) : DREPHIP_QR1(RR, NC, 4, false)))
-    if (nch <= 8) {
-        switch (R) {
-            case 8: rc = DREPHIP_QR(8, 8); break;
-            case 4: rc = DREPHIP_QR(4, 8); break;
-            case 2: rc = DREPHIP_QR(2, 8); break;
-            default: rc = DREPHIP_QR(1, 8); break;
+    uint32_t ni = scr ? scr->nitems : 0;
+    if (!scr) {
+        // column tile: the rule of the triangle's plan -- the widest (<= kApCols)
+        // that still gives every workgroup slot of the chip about four items
+        uint32_t C = kApCols;
+        auto nitems_for = [&](uint32_t c) { return (uint64_t)ngroups * ((N + c - 1) / c); };
+        while (C > kApMinCols && nitems_for(C) < 4ull * kApSlots) C /= 2;
+        if (nitems_for(C) + kXcds * 16ull >= (1ull << 32)) {
+            set_error("the rectangle's item list exceeds 2^32 entries: call it in row ranges");
+            return DREPHIP_ERR_UNSUPPORTED;
         }
-    } else if (nch <= 16) {
-        switch (R) {
-            case 8: rc = DREPHIP_QR(8, 16); break;
-            case 4: rc = DREPHIP_QR(4, 16); break;
-            case 2: rc = DREPHIP_QR(2, 16); break;
-            default: rc = DREPHIP_QR(1, 16); break;
-        }
-    } else {
-        switch (R) {
-            case 4: rc = DREPHIP_QR(4, 32); break;
-            case 2: rc = DREPHIP_QR(2, 32); break;
-            default: rc = DREPHIP_QR(1, 32); break;
+        // the plan is not cached: its key (Q, q0, q1, N, R, C) is not the
+        // triangle's, and planning is a few thousand groups on the host
+        uint64_t ni64;
+        ItemPlan plan = plan_rect_items(q0, q1, N, R, C);
+        const uint64_t gmax = plan.gmax;
+        if ((rc = expand_items<true>(ctx, std::move(plan), groups, "rect_items", R, C, st, (void **)&d_items, &ni64)))
+            return rc;
+        ni = (uint32_t)ni64;
+        if (getenv("DREPHIP_DEBUG")) {                  // the geometry this call runs at (the tests read it)
+            const uint64_t per = max_blocks(kApWG);     // items per k_allpairs_q dispatch (launch_q)
+            fprintf(stderr, "[drephip] rect plan: R %u C %u items %llu slots %llu gmax %llu pieces %u\n", R, C,
+                    (unsigned long long)nitems_for(C), (unsigned long long)ni64, (unsigned long long)gmax,
+                    (uint32_t)((ni64 + per - 1) / per));
         }
     }
-#undef DREPHIP_QR
-#undef DREPHIP_QR1
-    return rc;
+    // the unscreened flavours over the plan's items, or (scr) the LIST
+    // flavours over the screen's, where the geometry has them (the caller has
+    // checked: rect_list_geometry)
+    return q_dispatch(R, g, [&](auto t) {
+        using T = decltype(t);
+        auto run = [&](auto list, auto sparse) {
+            constexpr bool LIST = decltype(list)::value;
+            return launch_q<T::R, T::NCH, T::MINW, LIST, decltype(sparse)::value, true>(
+                ctx, ni, g, st, d_qh, d_qn, d_blk, d_fam, Q, q0, q1, LIST ? scr->items : d_items, d_common, d_denom, 0ull,
+                LIST ? scr->clist : nullptr, nullptr, out, cols);
+        };
+        if (!scr) return sp ? run(std::false_type{}, std::true_type{}) : run(std::false_type{}, std::false_type{});
+        if constexpr (T::rect_list) {
+            return sp ? run(std::true_type{}, std::true_type{}) : run(std::true_type{}, std::false_type{});
+        } else {
+            set_error("the screened rectangle has no kernel at this geometry");
+            return (int)DREPHIP_ERR_UNSUPPORTED;
+        }
+    });
 }
 
 // Rows [q0, q1) through the RECT flavour of the band kernel (launch_band's
 // geometry: R = 4, 2^11 slots, cap 768, two workgroups per CU; no value
-// rounds): the item plan, the launches, then the failure count.  When a band
-// table could not be built (nfail) the rows are rerun by k_rect_merge, as
-// launch_band_cfg reruns the triangle's, and ctx->rect_fallback is set.
-// Synchronises the stream before the rerun; the rerun itself is queued.
+// rounds): the item plan, the launches, then the failure count
+// (band_dispatch).  When a band table could not be built (nfail) the rows are
+// rerun by k_rect_merge, as launch_band_cfg reruns the triangle's, and
+// ctx->rect_fallback is set.  Synchronises the stream before the rerun; the
+// rerun itself is queued.
 // scr (the two-set screen's lists of these rows): the RECT, LIST flavour over
 // its items; a rerun still writes every cell of the rows.
 static int launch_rect_band(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q,
@@ -2340,12 +2349,17 @@ static int launch_rect_band(drephip_ctx *ctx, const uint64_t *d_qh, const uint32
                             const ScreenResult *scr = nullptr) {
     constexpr int R = kBandR, BB = 11, CAP = 768, MINW = 8;
     const uint32_t cap = std::min(std::max(ctx->rect_band_cap, 1u), (uint32_t)CAP);
+    int rc;
+    // the rows again by the exact merge kernel, every cell of them
+    auto rerun = [&]() {
+        ctx->rect_fallback = 1;
+        return launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
+    };
     {   // A query row whose last valid hash is 2^64 - 1 (the padding value; no
         // sketcher admits it) has no band bound above it (maxlast + 1 wraps):
         // such rows never reach the band kernel, the call's rows go to the
         // exact merge kernel as after an unbuildable table.
         uint32_t *d_max, h_max = 0;
-        int rc;
         if ((rc = scratch(ctx, "rect_last_max", 4, (void **)&d_max))) return rc;
         HIPC(hipMemsetAsync(d_max, 0, 4, st));
         hipLaunchKernelGGL(k_rect_last_is_max, dim3((q1 - q0 + 255) / 256), dim3(256), 0, st, d_qh, d_qn, ctx->s, q0, q1,
@@ -2353,78 +2367,40 @@ static int launch_rect_band(drephip_ctx *ctx, const uint64_t *d_qh, const uint32
         HIPC(hipGetLastError());
         HIPC(hipMemcpyAsync(&h_max, d_max, 4, hipMemcpyDeviceToHost, st));
         HIPC(hipStreamSynchronize(st));
-        if (h_max) {
-            ctx->rect_fallback = 1;
-            return launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
-        }
+        if (h_max) return rerun();
     }
-    if (scr) {
-        int rc;
-        const uint64_t per = max_blocks(1024);       // items per dispatch
-        if ((rc = rect_screen_plan_line(ctx, *scr, q1 - q0, R, kBandCols, (uint32_t)per, st))) return rc;
-        if (scr->nitems == 0) return DREPHIP_OK;
-        uint32_t *d_nfail;
-        if ((rc = scratch(ctx, "ap_nfail_band", 4, (void **)&d_nfail))) return rc;
-        HIPC(hipMemsetAsync(d_nfail, 0, 4, st));
-        constexpr size_t lds = band_lds_bytes<R, BB, CAP>();
-        auto kern = k_allpairs_band<R, BB, CAP, 1024, MINW, true, false, true>;
-        HIPC(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const RectCols cols{d_rh, d_rn, N};
-        timing_mark(ctx, 2, st, true);
-        for (uint64_t i0 = 0; i0 < scr->nitems; i0 += per)
-            hipLaunchKernelGGL(kern, dim3((uint32_t)std::min<uint64_t>(scr->nitems - i0, per)), dim3(1024), lds, st, d_qh,
-                               d_qn, ctx->s, Q, q1, cap, (const uint2 *)nullptr, d_common, d_denom, (uint64_t)q0 * N,
-                               d_nfail, (uint64_t *)nullptr, scr->items + i0, scr->clist, (uint32_t *)nullptr,
-                               (const uint64_t *)nullptr, 0u, cols);
-        timing_mark(ctx, 2, st, false);
-        HIPC(hipGetLastError());
-        uint32_t nfail = 0;
-        HIPC(hipMemcpyAsync(&nfail, d_nfail, 4, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-        if (nfail) {   // as below: the rows again by the exact merge kernel, every cell of them
-            ctx->rect_fallback = 1;
-            return launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
-        }
-        return DREPHIP_OK;
-    }
-    const uint64_t nrt = ((uint64_t)(q1 - q0) + R - 1) / R, nct = ((uint64_t)N + kBandCols - 1) / kBandCols;
-    if (nrt * nct + kXcds * 16ull >= (1ull << 32)) {
-        set_error("the rectangle's item list exceeds 2^32 entries: call it in row ranges");
-        return DREPHIP_ERR_UNSUPPORTED;
-    }
-    int rc;
-    uint2 *d_items = nullptr;
-    uint64_t nitems;
-    if ((rc = expand_items<false>(ctx, plan_rect_items(q0, q1, N, R, kBandCols), groups, "rectb_items", R, kBandCols,
-                                  st, (void **)&d_items, &nitems)))
-        return rc;
     const uint64_t per = max_blocks(1024);           // items per dispatch
-    if (getenv("DREPHIP_DEBUG"))                    // the geometry this call runs at (the tests read it)
-        fprintf(stderr, "[drephip] rect band plan: R %d C %u cap %u items %llu slots %llu pieces %u\n", R, kBandCols, cap,
-                (unsigned long long)(nrt * nct), (unsigned long long)nitems, (uint32_t)((nitems + per - 1) / per));
-    uint32_t *d_nfail;
-    if ((rc = scratch(ctx, "ap_nfail_band", 4, (void **)&d_nfail))) return rc;
-    HIPC(hipMemsetAsync(d_nfail, 0, 4, st));
-    constexpr size_t lds = band_lds_bytes<R, BB, CAP>();
-    auto kern = k_allpairs_band<R, BB, CAP, 1024, MINW, false, false, true>;
-    HIPC(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const RectCols cols{d_rh, d_rn, N};
-    timing_mark(ctx, 2, st, true);
-    for (uint64_t i0 = 0; i0 < nitems; i0 += per)
-        hipLaunchKernelGGL(kern, dim3((uint32_t)std::min<uint64_t>(nitems - i0, per)), dim3(1024), lds, st, d_qh, d_qn,
-                           ctx->s, Q, q1, cap, d_items + i0, d_common, d_denom, (uint64_t)q0 * N, d_nfail,
-                           (uint64_t *)nullptr, (const uint4 *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                           (const uint64_t *)nullptr, 0u, cols);
-    timing_mark(ctx, 2, st, false);
-    HIPC(hipGetLastError());
-    uint32_t nfail = 0;
-    HIPC(hipMemcpyAsync(&nfail, d_nfail, 4, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    if (nfail) {   // a band table could not be built with any field pair: exact merge kernel instead
-        ctx->rect_fallback = 1;
-        return launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
+    const uint64_t seg0 = (uint64_t)q0 * N;
+    uint32_t nfail;
+    // (nr = 1: DREPHIP_BAND_ROUND, and with it DREPHIP_BAND_CHUNK and
+    // DREPHIP_BAND_PROF, are the triangle's only)
+    if (scr) {
+        if ((rc = rect_screen_plan_line(ctx, *scr, q1 - q0, R, kBandCols, (uint32_t)per, st))) return rc;
+        // no cell is marked: nothing to launch, and no stream sync here (the
+        // triangle's screened path synchronises; this one's callers do, per block)
+        if (scr->nitems == 0) return DREPHIP_OK;
+        rc = band_dispatch<R, BB, CAP, MINW, true, true>(ctx, d_qh, d_qn, Q, q1, cap, seg0, nullptr, scr->items, scr->clist,
+                                                         scr->nitems, 1, cols, d_common, d_denom, st, &nfail);
+    } else {
+        const uint64_t nrt = ((uint64_t)(q1 - q0) + R - 1) / R, nct = ((uint64_t)N + kBandCols - 1) / kBandCols;
+        if (nrt * nct + kXcds * 16ull >= (1ull << 32)) {
+            set_error("the rectangle's item list exceeds 2^32 entries: call it in row ranges");
+            return DREPHIP_ERR_UNSUPPORTED;
+        }
+        uint2 *d_items = nullptr;
+        uint64_t nitems;
+        if ((rc = expand_items<false>(ctx, plan_rect_items(q0, q1, N, R, kBandCols), groups, "rectb_items", R, kBandCols,
+                                      st, (void **)&d_items, &nitems)))
+            return rc;
+        if (getenv("DREPHIP_DEBUG"))                    // the geometry this call runs at (the tests read it)
+            fprintf(stderr, "[drephip] rect band plan: R %d C %u cap %u items %llu slots %llu pieces %u\n", R, kBandCols, cap,
+                    (unsigned long long)(nrt * nct), (unsigned long long)nitems, (uint32_t)((nitems + per - 1) / per));
+        rc = band_dispatch<R, BB, CAP, MINW, false, true>(ctx, d_qh, d_qn, Q, q1, cap, seg0, d_items, nullptr, nullptr, nitems,
+                                                          1, cols, d_common, d_denom, st, &nfail);
     }
-    return DREPHIP_OK;
+    if (rc) return rc;
+    return nfail ? rerun() : DREPHIP_OK;
 }
 
 // the rectangle's kernel for this context: the whole-row table kernel when its
@@ -2467,18 +2443,14 @@ static int rect_path(drephip_ctx *ctx, bool force_merge, uint32_t *R, int *path)
 // unscreened kernel 0.013 ms per row; AUTO breaks even near 1100 rows.
 constexpr uint32_t kRectScreenMinQ = 2048;
 
-// The RECT, LIST flavours of k_allpairs_q are instantiated at the (R, chunks,
-// workgroups per CU) allpairs_geometry picks by itself for some s <= 2048 --
-// (8, 8, 2), (8, 16, 1), (4, 16, 2), (4, 32, 1), (2, 32, 2); an A/B override of
-// R (DREPHIP_AP_R) outside them keeps the unscreened plan.
+// Whether the screened (LIST) flavour of the rectangle's kernel exists at this
+// geometry: the band kernel's always, the whole-row kernel's where kQRows says
+// so; an A/B override of R (DREPHIP_AP_R) outside those keeps the unscreened plan.
 static bool rect_list_geometry(drephip_ctx *ctx, uint32_t R, int path) {
     if (path == DREPHIP_AP_BAND) return true;
-    const uint32_t s = ctx->s, nch = (s + 63) / 64;
-    uint32_t B = 4;
-    while ((1u << B) < 2 * s) B++;
-    const bool two = ((q_lds_bytes(R, 2u << B, s) / 4 + 3) & ~3ull) * 4 <= 80 * 1024;
-    return (R == 8 && nch <= 8 && two) || (R == 8 && nch > 8 && nch <= 16 && !two) ||
-           (R == 4 && nch > 8 && nch <= 16 && two) || (R == 4 && nch > 16 && !two) || (R == 2 && nch > 16 && two);
+    const QGeom g = q_geom(ctx->s, R);
+    const int i = q_row(R, g.nch);
+    return i >= 0 && kQRows[i].rect_list && kQRows[i].MINW == g.minw;
 }
 
 // Whether a call over `rows` query rows screens its blocks: never the merge

@@ -243,7 +243,7 @@ CAP_ITEMS = "2048"           # DREPHIP_MAX_LAUNCH_ITEMS: 8 workgroups per dispat
 
 @pytest.mark.parametrize("s", [64, 1000])
 def test_split_rect_launches_match_oracle(s, monkeypatch, capfd):
-    """launch_rect_q in pieces of 8 items: the rectangle and the records."""
+    """launch_q in pieces of 8 items: the rectangle and the records."""
     H, NH, nq, (ec, ed) = case(s)
     monkeypatch.setenv("DREPHIP_DEBUG", "1")
     monkeypatch.setenv("DREPHIP_MAX_LAUNCH_ITEMS", CAP_ITEMS)
