@@ -2212,15 +2212,26 @@ __global__ __launch_bounds__(256) void k_rect_last_is_max(const uint64_t *__rest
     if (n > 0 && qhashes[(uint64_t)q * s + n - 1] == kEmpty) *flag = 1u;
 }
 
-static int launch_rect_merge(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, const uint64_t *d_rh,
-                             const uint32_t *d_rn, uint32_t N, uint32_t q0, uint64_t cells, uint16_t *d_common,
-                             uint16_t *d_denom, hipStream_t st) {
-    const uint64_t per = max_blocks(256) * 256;      // pairs per dispatch
+// Where a block's counts go: the rectangle at common / denom (denom may be
+// null) -- the call's own, the block at its rows' offset, or (scratch) one
+// scratch rectangle every block reuses -- or, common null, records appended to
+// *sp by the table kernel itself.  fill_denom: a screened block's unlisted
+// cells get their denominators too, not zero counts only.
+struct RectOut {
+    uint16_t *common, *denom;
+    const SparseOut *sp;
+    bool fill_denom, scratch;
+};
+
+// rows [q0, q1) by the literal merge, every cell of them
+static int launch_rect_merge(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, const RectOut &out,
+                             hipStream_t st) {
+    const uint64_t cells = (uint64_t)(q1 - q0) * in.N, per = max_blocks(256) * 256;      // per: pairs per dispatch
     timing_mark(ctx, 2, st, true);
     for (uint64_t p0 = 0; p0 < cells; p0 += per) {
         const uint64_t np = std::min(per, cells - p0);
-        hipLaunchKernelGGL(k_rect_merge, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, st, d_qh, d_qn, d_rh, d_rn,
-                           ctx->s, N, q0, p0, np, d_common, d_denom);
+        hipLaunchKernelGGL(k_rect_merge, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, st, in.qh, in.qn, in.rh, in.rn,
+                           ctx->s, in.N, q0, p0, np, out.common, out.denom);
     }
     timing_mark(ctx, 2, st, false);
     HIPC(hipGetLastError());
@@ -2266,27 +2277,33 @@ static int rect_screen_plan_line(drephip_ctx *ctx, const ScreenResult &scr, uint
     return DREPHIP_OK;
 }
 
+// A plan of `nitems` items, with the idle slots join_lists may add, must stay
+// within the kernels' 32-bit item index
+static int rect_items_fit(uint64_t nitems) {
+    if (nitems + kXcds * 16ull < (1ull << 32)) return DREPHIP_OK;
+    set_error("the rectangle's item list exceeds 2^32 entries: call it in row ranges");
+    return DREPHIP_ERR_UNSUPPORTED;
+}
+
 // Rows [q0, q1) through the RECT flavour of the whole-row kernel: the query
-// rows' images by k_build_q32, the item plan, the launch.  sp == null: the
-// rectangle into d_common / d_denom; else records into *sp.  Queued on st.
-// scr (the two-set screen's lists of these rows, rect_screen.hip): the LIST
-// flavours over its items instead of the plan -- the geometries of
+// rows' images by k_build_q32, the item plan, the launch.  out.sp == null: the
+// rectangle into out.common / out.denom; else records into *out.sp.  Queued on
+// st.  scr (the two-set screen's lists of these rows, rect_screen.hip): the
+// LIST flavours over its items instead of the plan -- the geometries of
 // rect_list_geometry only; nothing is launched when no cell is marked.
-static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
-                      const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint32_t R, uint16_t *d_common,
-                      uint16_t *d_denom, const SparseOut *sp, std::vector<ItemGroup> &groups, hipStream_t st,
-                      const ScreenResult *scr = nullptr) {
+static int rect_table(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, uint32_t R, const RectOut &out,
+                      std::vector<ItemGroup> &groups, hipStream_t st, const ScreenResult *scr) {
     if (scr && rect_screen_plan_line(ctx, *scr, q1 - q0, R, kApCols, (uint32_t)max_blocks(kApWG), st)) return DREPHIP_ERR_HIP;
     if (scr && scr->nitems == 0) return DREPHIP_OK;
     const QGeom g = q_geom(ctx->s, R);
-    const uint32_t ngroups = (q1 - q0 + R - 1) / R;
+    const uint32_t ngroups = (q1 - q0 + R - 1) / R, N = in.N;
     uint32_t *d_blk;
     uint8_t *d_fam;
     uint4 *d_items = nullptr;
     int rc;
-    if ((rc = build_row_images(ctx, d_qh, d_qn, q0, q1, R, g, st, &d_blk, &d_fam))) return rc;
-    const RectCols cols{d_rh, d_rn, N};
-    const SparseOut out = sp ? *sp : SparseOut{};
+    if ((rc = build_row_images(ctx, in.qh, in.qn, q0, q1, R, g, st, &d_blk, &d_fam))) return rc;
+    const RectCols cols{in.rh, in.rn, N};
+    const SparseOut sp = out.sp ? *out.sp : SparseOut{};
     uint32_t ni = scr ? scr->nitems : 0;
     if (!scr) {
         // column tile: the rule of the triangle's plan -- the widest (<= kApCols)
@@ -2294,10 +2311,7 @@ static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_
         uint32_t C = kApCols;
         auto nitems_for = [&](uint32_t c) { return (uint64_t)ngroups * ((N + c - 1) / c); };
         while (C > kApMinCols && nitems_for(C) < 4ull * kApSlots) C /= 2;
-        if (nitems_for(C) + kXcds * 16ull >= (1ull << 32)) {
-            set_error("the rectangle's item list exceeds 2^32 entries: call it in row ranges");
-            return DREPHIP_ERR_UNSUPPORTED;
-        }
+        if ((rc = rect_items_fit(nitems_for(C)))) return rc;
         // the plan is not cached: its key (Q, q0, q1, N, R, C) is not the
         // triangle's, and planning is a few thousand groups on the host
         uint64_t ni64;
@@ -2321,12 +2335,12 @@ static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_
         auto run = [&](auto list, auto sparse) {
             constexpr bool LIST = decltype(list)::value;
             return launch_q<T::R, T::NCH, T::MINW, LIST, decltype(sparse)::value, true>(
-                ctx, ni, g, st, d_qh, d_qn, d_blk, d_fam, Q, q0, q1, LIST ? scr->items : d_items, d_common, d_denom, 0ull,
-                LIST ? scr->clist : nullptr, nullptr, out, cols);
+                ctx, ni, g, st, in.qh, in.qn, d_blk, d_fam, in.Q, q0, q1, LIST ? scr->items : d_items, out.common, out.denom,
+                0ull, LIST ? scr->clist : nullptr, nullptr, sp, cols);
         };
-        if (!scr) return sp ? run(std::false_type{}, std::true_type{}) : run(std::false_type{}, std::false_type{});
+        if (!scr) return out.sp ? run(std::false_type{}, std::true_type{}) : run(std::false_type{}, std::false_type{});
         if constexpr (T::rect_list) {
-            return sp ? run(std::true_type{}, std::true_type{}) : run(std::true_type{}, std::false_type{});
+            return out.sp ? run(std::true_type{}, std::true_type{}) : run(std::true_type{}, std::false_type{});
         } else {
             set_error("the screened rectangle has no kernel at this geometry");
             return (int)DREPHIP_ERR_UNSUPPORTED;
@@ -2343,17 +2357,15 @@ static int rect_table(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_
 // rerun itself is queued.
 // scr (the two-set screen's lists of these rows): the RECT, LIST flavour over
 // its items; a rerun still writes every cell of the rows.
-static int launch_rect_band(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q,
-                            const uint64_t *d_rh, const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1,
-                            uint16_t *d_common, uint16_t *d_denom, std::vector<ItemGroup> &groups, hipStream_t st,
-                            const ScreenResult *scr = nullptr) {
+static int launch_rect_band(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, const RectOut &out,
+                            std::vector<ItemGroup> &groups, hipStream_t st, const ScreenResult *scr) {
     constexpr int R = kBandR, BB = 11, CAP = 768, MINW = 8;
-    const uint32_t cap = std::min(std::max(ctx->rect_band_cap, 1u), (uint32_t)CAP);
+    const uint32_t cap = std::min(std::max(ctx->rect_band_cap, 1u), (uint32_t)CAP), N = in.N;
     int rc;
-    // the rows again by the exact merge kernel, every cell of them
+    // the rows again by the exact merge kernel
     auto rerun = [&]() {
         ctx->rect_fallback = 1;
-        return launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
+        return launch_rect_merge(ctx, in, q0, q1, out, st);
     };
     {   // A query row whose last valid hash is 2^64 - 1 (the padding value; no
         // sketcher admits it) has no band bound above it (maxlast + 1 wraps):
@@ -2362,15 +2374,15 @@ static int launch_rect_band(drephip_ctx *ctx, const uint64_t *d_qh, const uint32
         uint32_t *d_max, h_max = 0;
         if ((rc = scratch(ctx, "rect_last_max", 4, (void **)&d_max))) return rc;
         HIPC(hipMemsetAsync(d_max, 0, 4, st));
-        hipLaunchKernelGGL(k_rect_last_is_max, dim3((q1 - q0 + 255) / 256), dim3(256), 0, st, d_qh, d_qn, ctx->s, q0, q1,
-                           d_max);
+        hipLaunchKernelGGL(k_rect_last_is_max, dim3((q1 - q0 + 255) / 256), dim3(256), 0, st, in.qh, in.qn, ctx->s, q0,
+                           q1, d_max);
         HIPC(hipGetLastError());
         HIPC(hipMemcpyAsync(&h_max, d_max, 4, hipMemcpyDeviceToHost, st));
         HIPC(hipStreamSynchronize(st));
         if (h_max) return rerun();
     }
     const uint64_t per = max_blocks(1024);           // items per dispatch
-    const RectCols cols{d_rh, d_rn, N};
+    const RectCols cols{in.rh, in.rn, N};
     const uint64_t seg0 = (uint64_t)q0 * N;
     uint32_t nfail;
     // (nr = 1: DREPHIP_BAND_ROUND, and with it DREPHIP_BAND_CHUNK and
@@ -2380,14 +2392,11 @@ static int launch_rect_band(drephip_ctx *ctx, const uint64_t *d_qh, const uint32
         // no cell is marked: nothing to launch, and no stream sync here (the
         // triangle's screened path synchronises; this one's callers do, per block)
         if (scr->nitems == 0) return DREPHIP_OK;
-        rc = band_dispatch<R, BB, CAP, MINW, true, true>(ctx, d_qh, d_qn, Q, q1, cap, seg0, nullptr, scr->items, scr->clist,
-                                                         scr->nitems, 1, cols, d_common, d_denom, st, &nfail);
+        rc = band_dispatch<R, BB, CAP, MINW, true, true>(ctx, in.qh, in.qn, in.Q, q1, cap, seg0, nullptr, scr->items,
+                                                         scr->clist, scr->nitems, 1, cols, out.common, out.denom, st, &nfail);
     } else {
         const uint64_t nrt = ((uint64_t)(q1 - q0) + R - 1) / R, nct = ((uint64_t)N + kBandCols - 1) / kBandCols;
-        if (nrt * nct + kXcds * 16ull >= (1ull << 32)) {
-            set_error("the rectangle's item list exceeds 2^32 entries: call it in row ranges");
-            return DREPHIP_ERR_UNSUPPORTED;
-        }
+        if ((rc = rect_items_fit(nrt * nct))) return rc;
         uint2 *d_items = nullptr;
         uint64_t nitems;
         if ((rc = expand_items<false>(ctx, plan_rect_items(q0, q1, N, R, kBandCols), groups, "rectb_items", R, kBandCols,
@@ -2396,8 +2405,8 @@ static int launch_rect_band(drephip_ctx *ctx, const uint64_t *d_qh, const uint32
         if (getenv("DREPHIP_DEBUG"))                    // the geometry this call runs at (the tests read it)
             fprintf(stderr, "[drephip] rect band plan: R %d C %u cap %u items %llu slots %llu pieces %u\n", R, kBandCols, cap,
                     (unsigned long long)(nrt * nct), (unsigned long long)nitems, (uint32_t)((nitems + per - 1) / per));
-        rc = band_dispatch<R, BB, CAP, MINW, false, true>(ctx, d_qh, d_qn, Q, q1, cap, seg0, d_items, nullptr, nullptr, nitems,
-                                                          1, cols, d_common, d_denom, st, &nfail);
+        rc = band_dispatch<R, BB, CAP, MINW, false, true>(ctx, in.qh, in.qn, in.Q, q1, cap, seg0, d_items, nullptr, nullptr,
+                                                          nitems, 1, cols, out.common, out.denom, st, &nfail);
     }
     if (rc) return rc;
     return nfail ? rerun() : DREPHIP_OK;
@@ -2467,154 +2476,158 @@ static bool rect_screen_on(drephip_ctx *ctx, uint32_t N, uint32_t rows, uint32_t
     return N >= min_n && rows >= min_q;
 }
 
-// One block of query rows [b0, b1) by the call's kernel.  d_c / d_d: the
-// block's first row of the rectangle (null with records from the table
-// kernel, sp).  screened: the two-set screen first; when it keeps the block,
-// the rectangle is filled as no-shared-hash cells (denominators only with
-// fill_denom) and the LIST flavour runs on the marked cells, else -- the
-// verdict, or lists past their indices -- every item runs as without it.
-static int rect_block(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
-                      const uint32_t *d_rn, uint32_t N, uint32_t b0, uint32_t b1, uint32_t R, int path, uint16_t *d_c,
-                      uint16_t *d_d, const SparseOut *sp, bool screened, bool force, bool fill_denom,
-                      std::vector<ItemGroup> &groups, hipStream_t st) {
-    if (path == DREPHIP_AP_MERGE)
-        return launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, (uint64_t)(b1 - b0) * N, d_c, d_d, st);
-    ScreenResult scr;
-    const ScreenResult *use = nullptr;
-    int rc;
-    if (screened) {
-        if ((rc = rect_screen_block(ctx, d_qh, d_qn, d_rh, d_rn, N, b0, b1, R,
-                                    path == DREPHIP_AP_BAND ? kBandCols : kApCols, force, st, &scr)))
-            return rc;
-        if (scr.use) {
-            use = &scr;
-            if (d_c && (rc = rect_screen_fill(ctx, d_qn, d_rn, N, b0, b1, d_c, fill_denom ? d_d : nullptr, st))) return rc;
-        }
-    }
-    if (path == DREPHIP_AP_BAND)
-        return launch_rect_band(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, d_c, d_d, groups, st, use);
-    return rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, d_c, d_d, sp, groups, st, use);
-}
+// What a call's three forms settle before their first launch
+struct RectCall {
+    uint32_t R;            // query rows per tile of the call's kernel
+    int path;              // DREPHIP_AP_TABLE / _BAND / _MERGE
+    bool screened, force;  // the two-set screen runs in front of every block (force: without its verdict)
+    bool empty;            // no cell to compute: the call returns at once
+    // The host copy of a block's item plan, which a queued copy reads
+    // (expand_items).  It lives in the entry point's frame, so past the call's
+    // last stream synchronisation on every route; rect_blocks says why the
+    // next block may rewrite it.
+    std::vector<ItemGroup> groups;
+};
 
-int rect_device_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
-                     const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint16_t *d_common,
-                     uint16_t *d_denom, hipStream_t st, bool force_merge) {
-    if (ctx->apend.active) {
-        int rc = allpairs_wait_impl(ctx);
-        if (rc) return rc;
-    }
-    if (q1 > Q) q1 = Q;
-    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
-    uint32_t R;
-    int path, rc;
-    if ((rc = rect_path(ctx, force_merge, &R, &path))) return rc;
+// The prologue of the three forms, in the order they share: a pending
+// asynchronous call is waited for, q1 clipped, an empty call told apart; then
+// the kernel (rect_path), the statistics reset, the screen's decision.
+static int rect_begin(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t *q1, bool force_merge, RectCall *call) {
+    *call = RectCall{1, DREPHIP_AP_MERGE, false, false, true};
+    int rc;
+    if (ctx->apend.active && (rc = allpairs_wait_impl(ctx))) return rc;
+    if (*q1 > in.Q) *q1 = in.Q;
+    if (in.Q == 0 || in.N == 0 || q0 >= *q1) return DREPHIP_OK;
+    call->empty = false;
+    if ((rc = rect_path(ctx, force_merge, &call->R, &call->path))) return rc;
     ctx->last_screen = ScreenResult{};
     ctx->rect_screen = RectScreenStats{};
-    bool force;
-    if (rect_screen_on(ctx, N, q1 - q0, R, path, &force)) {
-        // screened: blocks of query rows whose bitmap and sort stay bounded
-        const uint32_t rows = rect_screen_block_rows(ctx, N, R);
-        for (uint32_t b0 = q0; b0 < q1;) {
-            const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
-            std::vector<ItemGroup> groups;           // lives until the block's stream sync
-            const uint64_t o = (uint64_t)(b0 - q0) * N;
-            if ((rc = rect_block(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, path, d_common + o,
-                                 d_denom ? d_denom + o : nullptr, nullptr, true, force, true, groups, st)))
-                return rc;
-            HIPC(hipStreamSynchronize(st));
-            b0 = b1;
-        }
-        return DREPHIP_OK;
-    }
-    std::vector<ItemGroup> groups;                   // lives until the stream sync below
-    if (path == DREPHIP_AP_MERGE)
-        rc = launch_rect_merge(ctx, d_qh, d_qn, d_rh, d_rn, N, q0, (uint64_t)(q1 - q0) * N, d_common, d_denom, st);
-    else if (path == DREPHIP_AP_BAND)
-        rc = launch_rect_band(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, d_common, d_denom, groups, st);
-    else
-        rc = rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, R, d_common, d_denom, nullptr, groups, st);
-    if (rc) return rc;
-    HIPC(hipStreamSynchronize(st));
+    call->screened = rect_screen_on(ctx, in.N, *q1 - q0, call->R, call->path, &call->force);
     return DREPHIP_OK;
 }
 
-constexpr uint64_t kRectBlockPairs = 1ull << 28;    // cells per scratch rectangle of the merge route's records
-
-// Query rows per scratch rectangle: at most kRectBlockPairs cells, at least
-// one row.  The environment variable `knob` (tests only) lowers it: a value
-// <= 0 is ignored.
-static uint32_t rect_block_rows(uint32_t N, const char *knob) {
-    uint32_t rows = (uint32_t)std::max<uint64_t>(1, kRectBlockPairs / N);
-    if (const char *e = getenv(knob))
-        if (atoi(e) > 0) rows = std::min<uint32_t>(rows, (uint32_t)atoi(e));
-    return rows;
+// One block of query rows [b0, b1) by the call's kernel, into `out` (the
+// block's first row).  Screened: the two-set screen first; when it keeps the
+// block, the rectangle is filled as no-shared-hash cells (out.fill_denom) and
+// the LIST flavour runs on the marked cells, else -- the verdict, or lists
+// past their indices -- every item runs as without it.
+static int rect_block(drephip_ctx *ctx, const RectSets &in, uint32_t b0, uint32_t b1, RectCall &call, const RectOut &out,
+                      hipStream_t st) {
+    if (call.path == DREPHIP_AP_MERGE) return launch_rect_merge(ctx, in, b0, b1, out, st);
+    const bool band = call.path == DREPHIP_AP_BAND;
+    ScreenResult scr;
+    const ScreenResult *use = nullptr;
+    int rc;
+    if (call.screened) {
+        if ((rc = rect_screen_block(ctx, in, b0, b1, call.R, band ? kBandCols : kApCols, call.force, st, &scr))) return rc;
+        if (scr.use) {
+            use = &scr;
+            if (out.common &&
+                (rc = rect_screen_fill(ctx, in, b0, b1, out.common, out.fill_denom ? out.denom : nullptr, st)))
+                return rc;
+        }
+    }
+    return band ? launch_rect_band(ctx, in, b0, b1, out, call.groups, st, use)
+                : rect_table(ctx, in, b0, b1, call.R, out, call.groups, st, use);
 }
 
-int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
-                     const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint4 *d_pairs, uint64_t cap,
+// The driver of the three forms: rows [q0, q1) in blocks of `rows`, each by
+// rect_block into `out` (the call's rectangle: at the block's offset), then
+// after(b0, b1) -- what the form queues behind a block -- then, with `sync`,
+// a stream synchronisation.
+//
+// call.groups, which a block's queued copy reads, is rewritten by the next
+// block's plan.  That is safe on every route: with `sync` the copy is over by
+// then; without it (the record form) the band launch has read its failure
+// count back, synchronising, before it returned, the merge kernel and the
+// screened launches (their items are the screen's, on the device) never touch
+// the vector, and the unscreened table kernel is given the range as one block.
+template <class After>
+static int rect_blocks(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, RectCall &call, uint32_t rows,
+                       const RectOut &out, bool sync, hipStream_t st, After &&after) {
+    int rc;
+    for (uint32_t b0 = q0; b0 < q1;) {
+        const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
+        RectOut blk = out;
+        if (out.common && !out.scratch) {
+            const uint64_t o = (uint64_t)(b0 - q0) * in.N;
+            blk.common += o;
+            if (blk.denom) blk.denom += o;
+        }
+        if ((rc = rect_block(ctx, in, b0, b1, call, blk, st)) || (rc = after(b0, b1))) return rc;
+        if (sync) HIPC(hipStreamSynchronize(st));
+        b0 = b1;
+    }
+    return DREPHIP_OK;
+}
+
+static int rect_no_after(uint32_t, uint32_t) { return DREPHIP_OK; }
+
+int rect_device_impl(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, uint16_t *d_common,
+                     uint16_t *d_denom, hipStream_t st, bool force_merge) {
+    RectCall call;
+    int rc;
+    if ((rc = rect_begin(ctx, in, q0, &q1, force_merge, &call)) || call.empty) return rc;
+    // screened: blocks of query rows whose bitmap and sort stay bounded; else one block
+    const uint32_t rows = call.screened ? rect_screen_block_rows(ctx, in.N, call.R) : q1 - q0;
+    return rect_blocks(ctx, in, q0, q1, call, rows, RectOut{d_common, d_denom, nullptr, true, false}, true, st, rect_no_after);
+}
+
+constexpr uint64_t kRectBlockPairs = 1ull << 28;    // cells per scratch rectangle
+
+// The scratch rectangle of the forms that read a block's cells back (records
+// by the band or merge kernel, best hits) and the query rows per block: at
+// most kRectBlockPairs cells, at least one row; screened: also within the
+// screen's own block bound.  The environment variable `knob` (tests only)
+// lowers the rows: a value <= 0 is ignored.  `pad` bytes more are allocated.
+static int rect_scratch(drephip_ctx *ctx, uint32_t N, uint32_t nrows, const RectCall &call, const char *knob, uint64_t pad,
+                        uint32_t *rows, uint16_t **d_c, uint16_t **d_d) {
+    *rows = (uint32_t)std::max<uint64_t>(1, kRectBlockPairs / N);
+    if (const char *e = getenv(knob))
+        if (atoi(e) > 0) *rows = std::min<uint32_t>(*rows, (uint32_t)atoi(e));
+    if (call.screened) *rows = std::min(*rows, rect_screen_block_rows(ctx, N, call.R));
+    const uint64_t bytes = (uint64_t)std::min(*rows, nrows) * N * 2 + pad;
+    if (int rc = scratch(ctx, "rect_blk_common", bytes, (void **)d_c)) return rc;
+    return scratch(ctx, "rect_blk_denom", bytes, (void **)d_d);
+}
+
+int rect_sparse_impl(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, uint4 *d_pairs, uint64_t cap,
                      uint64_t *n_pairs, hipStream_t st) {
     *n_pairs = 0;
-    if (ctx->apend.active) {
-        int rc = allpairs_wait_impl(ctx);
-        if (rc) return rc;
-    }
-    if (q1 > Q) q1 = Q;
-    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
-    uint32_t R;
-    int path, rc;
-    if ((rc = rect_path(ctx, false, &R, &path))) return rc;
-    ctx->last_screen = ScreenResult{};
-    ctx->rect_screen = RectScreenStats{};
-    bool force;
-    const bool screened = rect_screen_on(ctx, N, q1 - q0, R, path, &force);
+    RectCall call;
+    int rc;
+    if ((rc = rect_begin(ctx, in, q0, &q1, false, &call)) || call.empty) return rc;
     unsigned long long *d_count;
     uint64_t *h_tot;
     if ((rc = scratch(ctx, "sp_count", 8, (void **)&d_count))) return rc;
     if ((rc = pinned_host(ctx, "sp_tot", 64, (void **)&h_tot))) return rc;
     HIPC(hipMemsetAsync(d_count, 0, 8, st));
-    const SparseOut out{d_pairs, d_count, cap};
-    std::vector<ItemGroup> groups;                   // lives until the stream sync below
-    if (path == DREPHIP_AP_TABLE && screened) {
-        // the screen's row blocks; the LIST, SPARSE kernel appends straight from the lists
-        const uint32_t rows = rect_screen_block_rows(ctx, N, R);
-        for (uint32_t b0 = q0; b0 < q1;) {
-            const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
-            if ((rc = rect_block(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, path, nullptr, nullptr, &out, true, force,
-                                 false, groups, st)))
-                return rc;
-            HIPC(hipStreamSynchronize(st));          // `groups` is free for the next block
-            b0 = b1;
-        }
-    } else if (path == DREPHIP_AP_TABLE) {
-        if ((rc = rect_table(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, R, nullptr, nullptr, &out, groups, st))) return rc;
+    const SparseOut sp{d_pairs, d_count, cap};
+    if (call.path == DREPHIP_AP_TABLE) {
+        // the SPARSE kernel appends by itself: the screen's row blocks, each synchronised, or one queued block
+        const uint32_t rows = call.screened ? rect_screen_block_rows(ctx, in.N, call.R) : q1 - q0;
+        rc = rect_blocks(ctx, in, q0, q1, call, rows, RectOut{nullptr, nullptr, &sp, false, false}, call.screened, st,
+                         rect_no_after);
     } else {
-        // query-row blocks of at most kRectBlockPairs cells (at least one row);
-        // screened: also within the screen's own block bound -- one loop
-        uint32_t rows = rect_block_rows(N, "DREPHIP_RECT_BLOCK_ROWS");
-        if (screened) rows = std::min(rows, rect_screen_block_rows(ctx, N, R));
-        const uint64_t bcells = (uint64_t)std::min<uint32_t>(rows, q1 - q0) * N;
+        // blocks into the scratch rectangle, its non-zero cells compacted behind
+        // each.  A screened block is filled with zero counts only: the compaction
+        // reads a denominator where the count is not zero, a listed cell.
+        uint32_t rows;
         uint16_t *d_c, *d_d;
-        if ((rc = scratch(ctx, "rect_blk_common", bcells * 2, (void **)&d_c))) return rc;
-        if ((rc = scratch(ctx, "rect_blk_denom", bcells * 2, (void **)&d_d))) return rc;
-        for (uint32_t b0 = q0; b0 < q1;) {
-            const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
-            const uint64_t cells = (uint64_t)(b1 - b0) * N;
-            // (the band kernel's launch synchronises: `groups` is free for the next block);
-            // a screened block is filled with zero counts only: the compaction
-            // reads a denominator where the count is not zero, a listed cell
-            if ((rc = rect_block(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, path, d_c, d_d, nullptr, screened, force,
-                                 false, groups, st)))
-                return rc;
-            const uint64_t per = max_blocks(256) * 256;
-            for (uint64_t p0 = 0; p0 < cells; p0 += per) {
-                const uint64_t np = std::min(per, cells - p0);
-                hipLaunchKernelGGL(k_rect_compact, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, st, d_c, d_d, N, b0,
-                                   p0, np, out);
-            }
-            HIPC(hipGetLastError());
-            b0 = b1;
-        }
+        if ((rc = rect_scratch(ctx, in.N, q1 - q0, call, "DREPHIP_RECT_BLOCK_ROWS", 0, &rows, &d_c, &d_d))) return rc;
+        rc = rect_blocks(ctx, in, q0, q1, call, rows, RectOut{d_c, d_d, nullptr, false, true}, false, st,
+                         [&](uint32_t b0, uint32_t b1) -> int {
+                             const uint64_t cells = (uint64_t)(b1 - b0) * in.N, per = max_blocks(256) * 256;
+                             for (uint64_t p0 = 0; p0 < cells; p0 += per) {
+                                 const uint64_t np = std::min(per, cells - p0);
+                                 hipLaunchKernelGGL(k_rect_compact, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, st, d_c,
+                                                    d_d, in.N, b0, p0, np, sp);
+                             }
+                             HIPC(hipGetLastError());
+                             return DREPHIP_OK;
+                         });
     }
+    if (rc) return rc;
     HIPC(hipMemcpyAsync(h_tot, d_count, 8, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     const uint64_t total = h_tot[0];
@@ -2626,47 +2639,25 @@ int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_q
     return DREPHIP_OK;
 }
 
-int rect_top_impl(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, uint32_t Q, const uint64_t *d_rh,
-                  const uint32_t *d_rn, uint32_t N, uint32_t q0, uint32_t q1, uint32_t top, uint32_t *d_hits,
+int rect_top_impl(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, uint32_t top, uint32_t *d_hits,
                   uint32_t *d_count, hipStream_t st) {
-    if (ctx->apend.active) {
-        int rc = allpairs_wait_impl(ctx);
-        if (rc) return rc;
-    }
-    if (q1 > Q) q1 = Q;
-    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
-    uint32_t R;
-    int path, rc;
-    if ((rc = rect_path(ctx, false, &R, &path))) return rc;
-    ctx->last_screen = ScreenResult{};
-    ctx->rect_screen = RectScreenStats{};
-    bool force;
-    const bool screened = rect_screen_on(ctx, N, q1 - q0, R, path, &force);
-    // query-row blocks of at most kRectBlockPairs cells (at least one row), as
-    // the record form's merge route; screened: also within the screen's own
-    // block bound -- one loop
-    uint32_t rows = rect_block_rows(N, "DREPHIP_RECT_TOP_BLOCK_ROWS");
-    if (screened) rows = std::min(rows, rect_screen_block_rows(ctx, N, R));
-    const uint64_t bcells = (uint64_t)std::min<uint32_t>(rows, q1 - q0) * N;
+    RectCall call;
+    int rc;
+    if ((rc = rect_begin(ctx, in, q0, &q1, false, &call)) || call.empty) return rc;
+    uint32_t rows;
     uint16_t *d_c, *d_d;
     // 16 bytes more: k_rect_top reads whole 16-byte words up to the last row's end
-    if ((rc = scratch(ctx, "rect_blk_common", bcells * 2 + 16, (void **)&d_c))) return rc;
-    if ((rc = scratch(ctx, "rect_blk_denom", bcells * 2 + 16, (void **)&d_d))) return rc;
-    for (uint32_t b0 = q0; b0 < q1;) {
-        const uint32_t b1 = (uint32_t)std::min<uint64_t>(q1, (uint64_t)b0 + rows);
-        std::vector<ItemGroup> groups;               // lives until the block's stream sync
-        if ((rc = rect_block(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, b0, b1, R, path, d_c, d_d, nullptr, screened, force, true,
-                             groups, st)))
-            return rc;
-        timing_mark(ctx, 5, st, true);
-        hipLaunchKernelGGL(k_rect_top, dim3((uint32_t)std::min<uint64_t>(b1 - b0, max_blocks(kTopWG))), dim3(kTopWG), 0, st,
-                           d_c, d_d, N, b1 - b0, top, d_hits + (uint64_t)(b0 - q0) * top * 4, d_count + (b0 - q0));
-        timing_mark(ctx, 5, st, false);
-        HIPC(hipGetLastError());
-        HIPC(hipStreamSynchronize(st));
-        b0 = b1;
-    }
-    return DREPHIP_OK;
+    if ((rc = rect_scratch(ctx, in.N, q1 - q0, call, "DREPHIP_RECT_TOP_BLOCK_ROWS", 16, &rows, &d_c, &d_d))) return rc;
+    return rect_blocks(ctx, in, q0, q1, call, rows, RectOut{d_c, d_d, nullptr, true, true}, true, st,
+                       [&](uint32_t b0, uint32_t b1) -> int {
+                           timing_mark(ctx, 5, st, true);
+                           hipLaunchKernelGGL(k_rect_top, dim3((uint32_t)std::min<uint64_t>(b1 - b0, max_blocks(kTopWG))),
+                                              dim3(kTopWG), 0, st, d_c, d_d, in.N, b1 - b0, top,
+                                              d_hits + (uint64_t)(b0 - q0) * top * 4, d_count + (b0 - q0));
+                           timing_mark(ctx, 5, st, false);
+                           HIPC(hipGetLastError());
+                           return DREPHIP_OK;
+                       });
 }
 
 // Completes a deferred table-path call (drephip_allpairs_device_async): waits

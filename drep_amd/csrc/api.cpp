@@ -1390,42 +1390,37 @@ DREPHIP_EXPORT int drephip_allpairs_sparse(drephip_ctx *ctx, const uint64_t *has
 // ------------------------------------------------- query against reference
 // `mash dist <reference.msh> <query.msh>`: the Q x N rectangle (allpairs.hip,
 // rect_device_impl / rect_sparse_impl)
-static bool rect_null(const void *a, const void *b, uint32_t Q, const void *c, const void *d, uint32_t N) {
-    return (Q && (!a || !b)) || (N && (!c || !d));
+static bool rect_null(const RectSets &in) {
+    return (in.Q && (!in.qh || !in.qn)) || (in.N && (!in.rh || !in.rn));
+}
+
+// the body of the two dense device forms
+static int rect_dense_device(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, uint16_t *d_common,
+                             uint16_t *d_denom, void *stream, bool force_merge) {
+    GUARD_CTX(ctx);
+    if (rect_null(in) || (in.Q && in.N && q0 < q1 && !d_common)) {
+        set_error("null argument");
+        return DREPHIP_ERR_ARG;
+    }
+    timing_begin(ctx);
+    int rc = rect_device_impl(ctx, in, q0, q1, d_common, d_denom, pick_stream(ctx, stream), force_merge);
+    if (rc) return rc;
+    timing_collect(ctx);
+    return DREPHIP_OK;
 }
 
 DREPHIP_EXPORT int drephip_dist_rect_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash,
                                             uint32_t Q, const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N,
                                             uint32_t q0, uint32_t q1, uint16_t *d_common, uint16_t *d_denom,
                                             void *stream) {
-    GUARD_CTX(ctx);
-    if (rect_null(d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N) || (Q && N && q0 < q1 && !d_common)) {
-        set_error("null argument");
-        return DREPHIP_ERR_ARG;
-    }
-    timing_begin(ctx);
-    int rc = rect_device_impl(ctx, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1, d_common, d_denom,
-                              pick_stream(ctx, stream), false);
-    if (rc) return rc;
-    timing_collect(ctx);
-    return DREPHIP_OK;
+    return rect_dense_device(ctx, {d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N}, q0, q1, d_common, d_denom, stream, false);
 }
 
 DREPHIP_EXPORT int drephip_dist_rect_merge_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash,
                                                   uint32_t Q, const uint64_t *d_rhashes, const uint32_t *d_rnhash,
                                                   uint32_t N, uint32_t q0, uint32_t q1, uint16_t *d_common,
                                                   uint16_t *d_denom, void *stream) {
-    GUARD_CTX(ctx);
-    if (rect_null(d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N) || (Q && N && q0 < q1 && !d_common)) {
-        set_error("null argument");
-        return DREPHIP_ERR_ARG;
-    }
-    timing_begin(ctx);
-    int rc = rect_device_impl(ctx, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1, d_common, d_denom,
-                              pick_stream(ctx, stream), true);
-    if (rc) return rc;
-    timing_collect(ctx);
-    return DREPHIP_OK;
+    return rect_dense_device(ctx, {d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N}, q0, q1, d_common, d_denom, stream, true);
 }
 
 // a host sketch matrix as the kernels need it: nhash <= s, rows ascending and
@@ -1442,21 +1437,32 @@ static int check_rows(const uint64_t *hashes, const uint32_t *nhash, uint32_t n,
     return DREPHIP_OK;
 }
 
-// both matrices of a host rectangle call onto the context's device
-static int rect_stage(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash, uint32_t Q,
-                      const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint64_t **d_qh, uint32_t **d_qn,
-                      uint64_t **d_rh, uint32_t **d_rn) {
+// What the three host forms share once their inputs are known not to be null
+// (each form tests that itself: the tests that go with it differ): q1 clipped,
+// an empty call told apart (*empty: the form returns at once), the form's
+// outputs tested (out_null), both matrices checked and staged onto the
+// context's device (*dev).
+static int rect_host_stage(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t *q1, bool out_null, RectSets *dev,
+                           bool *empty) {
+    if (*q1 > in.Q) *q1 = in.Q;
+    *empty = in.Q == 0 || in.N == 0 || q0 >= *q1;
+    if (*empty) return DREPHIP_OK;
+    if (out_null) { set_error("null argument"); return DREPHIP_ERR_ARG; }
     int rc;
-    const uint32_t s = ctx->s;
+    if ((rc = check_rows(in.qh, in.qn, in.Q, ctx->s)) || (rc = check_rows(in.rh, in.rn, in.N, ctx->s))) return rc;
+    const uint64_t qbytes = (uint64_t)in.Q * ctx->s * 8, rbytes = (uint64_t)in.N * ctx->s * 8;
     hipStream_t st = ctx->stream;
-    if ((rc = scratch(ctx, "rect_in_qh", (uint64_t)Q * s * 8, (void **)d_qh))) return rc;
-    if ((rc = scratch(ctx, "rect_in_qn", Q * 4ull, (void **)d_qn))) return rc;
-    if ((rc = scratch(ctx, "rect_in_rh", (uint64_t)N * s * 8, (void **)d_rh))) return rc;
-    if ((rc = scratch(ctx, "rect_in_rn", N * 4ull, (void **)d_rn))) return rc;
-    HIPC(hipMemcpyAsync(*d_qh, qhashes, (uint64_t)Q * s * 8, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(*d_qn, qnhash, Q * 4ull, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(*d_rh, rhashes, (uint64_t)N * s * 8, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(*d_rn, rnhash, N * 4ull, hipMemcpyHostToDevice, st));
+    uint64_t *d_qh, *d_rh;
+    uint32_t *d_qn, *d_rn;
+    if ((rc = scratch(ctx, "rect_in_qh", qbytes, (void **)&d_qh))) return rc;
+    if ((rc = scratch(ctx, "rect_in_qn", in.Q * 4ull, (void **)&d_qn))) return rc;
+    if ((rc = scratch(ctx, "rect_in_rh", rbytes, (void **)&d_rh))) return rc;
+    if ((rc = scratch(ctx, "rect_in_rn", in.N * 4ull, (void **)&d_rn))) return rc;
+    HIPC(hipMemcpyAsync(d_qh, in.qh, qbytes, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_qn, in.qn, in.Q * 4ull, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_rh, in.rh, rbytes, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_rn, in.rn, in.N * 4ull, hipMemcpyHostToDevice, st));
+    *dev = RectSets{d_qh, d_qn, in.Q, d_rh, d_rn, in.N};
     return DREPHIP_OK;
 }
 
@@ -1464,22 +1470,19 @@ DREPHIP_EXPORT int drephip_dist_rect(drephip_ctx *ctx, const uint64_t *qhashes, 
                                      const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint32_t q0,
                                      uint32_t q1, uint16_t *common_out, uint16_t *denom_out) {
     GUARD_CTX(ctx);
-    if (rect_null(qhashes, qnhash, Q, rhashes, rnhash, N)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    if (q1 > Q) q1 = Q;
-    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
-    if (!common_out) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    const RectSets in{qhashes, qnhash, Q, rhashes, rnhash, N};
+    if (rect_null(in)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    RectSets dev;
+    bool empty;
     int rc;
-    if ((rc = check_rows(qhashes, qnhash, Q, ctx->s)) || (rc = check_rows(rhashes, rnhash, N, ctx->s))) return rc;
+    if ((rc = rect_host_stage(ctx, in, q0, &q1, !common_out, &dev, &empty)) || empty) return rc;
     hipStream_t st = ctx->stream;
-    uint64_t *d_qh, *d_rh;
-    uint32_t *d_qn, *d_rn;
     uint16_t *d_c, *d_d = nullptr;
     const uint64_t cells = (uint64_t)(q1 - q0) * N;
-    if ((rc = rect_stage(ctx, qhashes, qnhash, Q, rhashes, rnhash, N, &d_qh, &d_qn, &d_rh, &d_rn))) return rc;
     if ((rc = scratch(ctx, "rect_out_c", cells * 2, (void **)&d_c))) return rc;
     if (denom_out && (rc = scratch(ctx, "rect_out_d", cells * 2, (void **)&d_d))) return rc;
     timing_begin(ctx);
-    if ((rc = rect_device_impl(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, d_c, d_d, st, false))) return rc;
+    if ((rc = rect_device_impl(ctx, dev, q0, q1, d_c, d_d, st, false))) return rc;
     timing_collect(ctx);
     HIPC(hipMemcpyAsync(common_out, d_c, cells * 2, hipMemcpyDeviceToHost, st));
     if (denom_out) HIPC(hipMemcpyAsync(denom_out, d_d, cells * 2, hipMemcpyDeviceToHost, st));
@@ -1492,13 +1495,13 @@ DREPHIP_EXPORT int drephip_dist_rect_sparse_device(drephip_ctx *ctx, const uint6
                                                    const uint32_t *d_rnhash, uint32_t N, uint32_t q0, uint32_t q1,
                                                    uint32_t *d_pairs, uint64_t cap, uint64_t *n_pairs, void *stream) {
     GUARD_CTX(ctx);
-    if (rect_null(d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N) || !n_pairs || (cap && !d_pairs)) {
+    const RectSets in{d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N};
+    if (rect_null(in) || !n_pairs || (cap && !d_pairs)) {
         set_error("null argument");
         return DREPHIP_ERR_ARG;
     }
     timing_begin(ctx);
-    int rc = rect_sparse_impl(ctx, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1, (uint4 *)d_pairs, cap,
-                              n_pairs, pick_stream(ctx, stream));
+    int rc = rect_sparse_impl(ctx, in, q0, q1, (uint4 *)d_pairs, cap, n_pairs, pick_stream(ctx, stream));
     if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
     timing_collect(ctx);
     return rc;
@@ -1509,22 +1512,21 @@ DREPHIP_EXPORT int drephip_dist_rect_sparse(drephip_ctx *ctx, const uint64_t *qh
                                             uint32_t q0, uint32_t q1, uint32_t *pairs, uint64_t cap,
                                             uint64_t *n_pairs) {
     GUARD_CTX(ctx);
-    if (rect_null(qhashes, qnhash, Q, rhashes, rnhash, N) || !n_pairs || (cap && !pairs)) {
+    const RectSets in{qhashes, qnhash, Q, rhashes, rnhash, N};
+    if (rect_null(in) || !n_pairs || (cap && !pairs)) {
         set_error("null argument");
         return DREPHIP_ERR_ARG;
     }
     *n_pairs = 0;
-    if (q1 > Q) q1 = Q;
-    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
+    RectSets dev;
+    bool empty;
     int rc;
-    if ((rc = check_rows(qhashes, qnhash, Q, ctx->s)) || (rc = check_rows(rhashes, rnhash, N, ctx->s))) return rc;
+    if ((rc = rect_host_stage(ctx, in, q0, &q1, false, &dev, &empty)) || empty) return rc;
     hipStream_t st = ctx->stream;
-    uint64_t *d_qh, *d_rh;
-    uint32_t *d_qn, *d_rn, *d_p = nullptr;
-    if ((rc = rect_stage(ctx, qhashes, qnhash, Q, rhashes, rnhash, N, &d_qh, &d_qn, &d_rh, &d_rn))) return rc;
+    uint32_t *d_p = nullptr;
     if (cap && (rc = scratch(ctx, "rect_sp_out", cap * 16, (void **)&d_p))) return rc;
     timing_begin(ctx);
-    rc = rect_sparse_impl(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, (uint4 *)d_p, cap, n_pairs, st);
+    rc = rect_sparse_impl(ctx, dev, q0, q1, (uint4 *)d_p, cap, n_pairs, st);
     if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
     timing_collect(ctx);
     const uint64_t have = std::min(*n_pairs, cap);
@@ -1543,16 +1545,15 @@ DREPHIP_EXPORT int drephip_dist_rect_top_device(drephip_ctx *ctx, const uint64_t
                                                 uint32_t N, uint32_t q0, uint32_t q1, uint32_t top, uint32_t *d_hits,
                                                 uint32_t *d_count, void *stream) {
     GUARD_CTX(ctx);
-    if (rect_null(d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N) || (Q && N && q0 < q1 && (!d_hits || !d_count))) {
+    const RectSets in{d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N};
+    if (rect_null(in) || (Q && N && q0 < q1 && (!d_hits || !d_count))) {
         set_error("null argument");
         return DREPHIP_ERR_ARG;
     }
     int rc;
     if ((rc = rect_top_args(top))) return rc;
     timing_begin(ctx);
-    if ((rc = rect_top_impl(ctx, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1, top, d_hits, d_count,
-                            pick_stream(ctx, stream))))
-        return rc;
+    if ((rc = rect_top_impl(ctx, in, q0, q1, top, d_hits, d_count, pick_stream(ctx, stream)))) return rc;
     timing_collect(ctx);
     return DREPHIP_OK;
 }
@@ -1561,22 +1562,20 @@ DREPHIP_EXPORT int drephip_dist_rect_top(drephip_ctx *ctx, const uint64_t *qhash
                                          const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint32_t q0,
                                          uint32_t q1, uint32_t top, uint32_t *hits, uint32_t *count) {
     GUARD_CTX(ctx);
-    if (rect_null(qhashes, qnhash, Q, rhashes, rnhash, N)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    const RectSets in{qhashes, qnhash, Q, rhashes, rnhash, N};
+    if (rect_null(in)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    RectSets dev;
+    bool empty;
     int rc;
     if ((rc = rect_top_args(top))) return rc;
-    if (q1 > Q) q1 = Q;
-    if (Q == 0 || N == 0 || q0 >= q1) return DREPHIP_OK;
-    if (!hits || !count) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    if ((rc = check_rows(qhashes, qnhash, Q, ctx->s)) || (rc = check_rows(rhashes, rnhash, N, ctx->s))) return rc;
+    if ((rc = rect_host_stage(ctx, in, q0, &q1, !hits || !count, &dev, &empty)) || empty) return rc;
     hipStream_t st = ctx->stream;
-    uint64_t *d_qh, *d_rh;
-    uint32_t *d_qn, *d_rn, *d_h, *d_n;
+    uint32_t *d_h, *d_n;
     const uint64_t rows = q1 - q0;
-    if ((rc = rect_stage(ctx, qhashes, qnhash, Q, rhashes, rnhash, N, &d_qh, &d_qn, &d_rh, &d_rn))) return rc;
     if ((rc = scratch(ctx, "rect_top_hits", rows * top * 16, (void **)&d_h))) return rc;
     if ((rc = scratch(ctx, "rect_top_count", rows * 4, (void **)&d_n))) return rc;
     timing_begin(ctx);
-    if ((rc = rect_top_impl(ctx, d_qh, d_qn, Q, d_rh, d_rn, N, q0, q1, top, d_h, d_n, st))) return rc;
+    if ((rc = rect_top_impl(ctx, dev, q0, q1, top, d_h, d_n, st))) return rc;
     timing_collect(ctx);
     HIPC(hipMemcpyAsync(hits, d_h, rows * top * 16, hipMemcpyDeviceToHost, st));
     HIPC(hipMemcpyAsync(count, d_n, rows * 4, hipMemcpyDeviceToHost, st));

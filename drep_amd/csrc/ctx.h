@@ -348,6 +348,17 @@ struct ScreenProf {
 int screen_lists(drephip_ctx *ctx, const uint32_t *d_bl, uint32_t ntiles, uint32_t NW, uint32_t C, uint32_t row0,
                  uint32_t R, const unsigned long long *d_nsimple, hipStream_t st, ScreenProf &prof, ScreenResult *res);
 
+// The two sets of a query-against-reference call, device pointers: the Q query
+// sketches and the N reference sketches (rows of ctx->s hashes, their counts)
+struct RectSets {
+    const uint64_t *qh;
+    const uint32_t *qn;
+    uint32_t Q;
+    const uint64_t *rh;
+    const uint32_t *rn;
+    uint32_t N;
+};
+
 // The rectangle's two-set screen (rect_screen.hip).  rect_screen_block: query
 // rows [b0, b1) joined against the reference matrix; res->use: the LIST items
 // (row tiles of R rows from b0, at most C columns each) replace the block's
@@ -355,11 +366,10 @@ int screen_lists(drephip_ctx *ctx, const uint32_t *d_bl, uint32_t ntiles, uint32
 // (not under force) or the lists' bail-out sends the block to every item.
 // Synchronises the stream.
 uint32_t rect_screen_block_rows(drephip_ctx *ctx, uint32_t N, uint32_t R);
-int rect_screen_block(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, const uint64_t *d_rh,
-                      const uint32_t *d_rn, uint32_t N, uint32_t b0, uint32_t b1, uint32_t R, uint32_t C, bool force,
+int rect_screen_block(drephip_ctx *ctx, const RectSets &in, uint32_t b0, uint32_t b1, uint32_t R, uint32_t C, bool force,
                       hipStream_t st, ScreenResult *res);
-int rect_screen_fill(drephip_ctx *ctx, const uint32_t *d_qn, const uint32_t *d_rn, uint32_t N, uint32_t b0,
-                     uint32_t b1, uint16_t *d_common, uint16_t *d_denom, hipStream_t st);
+int rect_screen_fill(drephip_ctx *ctx, const RectSets &in, uint32_t b0, uint32_t b1, uint16_t *d_common,
+                     uint16_t *d_denom, hipStream_t st);
 
 constexpr uint32_t kListCols = 512;             // screened columns per whole-row LIST item
 
@@ -385,20 +395,17 @@ uint64_t allpairs_image_bytes_per_row(drephip_ctx *ctx, uint32_t R);
 // flavour of the whole-row kernel (s <= 2048), the RECT flavour of the band
 // kernel above (ctx->rect_band) or (force_merge, DREPHIP_AP_MERGE,
 // DREPHIP_RECT_BAND_OFF above 2048) k_rect_merge.  Blocking.
-int rect_device_impl(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
-                     const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0, uint32_t q1,
-                     uint16_t *d_common, uint16_t *d_denom, hipStream_t st, bool force_merge);
+int rect_device_impl(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, uint16_t *d_common,
+                     uint16_t *d_denom, hipStream_t st, bool force_merge);
 // The same rows as records {q, r, common, denom} of the pairs with common > 0
 // (the contract of allpairs_sparse_impl).  Blocking.
-int rect_sparse_impl(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
-                     const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0, uint32_t q1,
-                     uint4 *d_pairs, uint64_t cap, uint64_t *n_pairs, hipStream_t st);
+int rect_sparse_impl(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, uint4 *d_pairs, uint64_t cap,
+                     uint64_t *n_pairs, hipStream_t st);
 // Per query row the `top` nearest references among those with common > 0, as
 // hits {r, common, denom, 0} (the contract of drephip_dist_rect_top_device):
 // query-row blocks into a scratch rectangle, k_rect_top after each.  Blocking.
-int rect_top_impl(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash, uint32_t Q,
-                  const uint64_t *d_rhashes, const uint32_t *d_rnhash, uint32_t N, uint32_t q0, uint32_t q1,
-                  uint32_t top, uint32_t *d_hits, uint32_t *d_count, hipStream_t st);
+int rect_top_impl(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, uint32_t top, uint32_t *d_hits,
+                  uint32_t *d_count, hipStream_t st);
 
 // Primary clustering (linkage.hip).
 int linkage_device_impl(drephip_ctx *ctx, double *d_D, uint32_t n, int method, double *Z_out, hipStream_t st);

@@ -209,9 +209,10 @@ static bool rect_screen_worth(uint32_t rows, uint32_t N, uint32_t s, uint64_t ch
     return (double)checks * ratio <= (double)rows * (double)N * (double)s;
 }
 
-int rect_screen_block(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_qn, const uint64_t *d_rh,
-                      const uint32_t *d_rn, uint32_t N, uint32_t b0, uint32_t b1, uint32_t R, uint32_t C, bool force,
+int rect_screen_block(drephip_ctx *ctx, const RectSets &in, uint32_t b0, uint32_t b1, uint32_t R, uint32_t C, bool force,
                       hipStream_t st, ScreenResult *res) {
+    const uint64_t *d_qh = in.qh, *d_rh = in.rh;
+    const uint32_t *d_qn = in.qn, *d_rn = in.rn, N = in.N;
     *res = ScreenResult{};
     RectScreenStats &S = ctx->rect_screen;
     const uint32_t s = ctx->s, nrows = b1 - b0;
@@ -323,13 +324,13 @@ int rect_screen_block(drephip_ctx *ctx, const uint64_t *d_qh, const uint32_t *d_
 // The block's cells as no-shared-hash cells: common 0 and, when wanted, denom
 // min(s, nq + nr); the LIST kernels then overwrite the listed cells.  d_common /
 // d_denom: the block's first row.
-int rect_screen_fill(drephip_ctx *ctx, const uint32_t *d_qn, const uint32_t *d_rn, uint32_t N, uint32_t b0,
-                     uint32_t b1, uint16_t *d_common, uint16_t *d_denom, hipStream_t st) {
+int rect_screen_fill(drephip_ctx *ctx, const RectSets &in, uint32_t b0, uint32_t b1, uint16_t *d_common,
+                     uint16_t *d_denom, hipStream_t st) {
     RsPhases ph(ctx, st);
-    HIPC(hipMemsetAsync(d_common, 0, (uint64_t)(b1 - b0) * N * 2, st));
+    HIPC(hipMemsetAsync(d_common, 0, (uint64_t)(b1 - b0) * in.N * 2, st));
     if (d_denom) {
-        hipLaunchKernelGGL(k_rs_denoms, dim3(std::min<uint32_t>(b1 - b0, 65535u)), dim3(kRsWG), 0, st, d_qn, d_rn, ctx->s,
-                           N, b0, b1 - b0, d_denom);
+        hipLaunchKernelGGL(k_rs_denoms, dim3(std::min<uint32_t>(b1 - b0, 65535u)), dim3(kRsWG), 0, st, in.qn, in.rn, ctx->s,
+                           in.N, b0, b1 - b0, d_denom);
         HIPC(hipGetLastError());
     }
     ph.end(4);
