@@ -1,21 +1,17 @@
 // api.cpp -- the extern "C" surface of libdrephip.so (include/drephip.h).
-// Host glue only: argument checks, device scratch, host<->device staging,
-// threads for FASTA ingest.  All sketch/dist arithmetic runs in the HIP
-// kernels of sketch.hip and allpairs.hip.
+// Host glue only: argument checks, device scratch, host<->device staging.
+// All sketch/dist arithmetic runs in the HIP kernels of sketch.hip and
+// allpairs.hip; the FASTA ingest is ingest_pipeline.cpp.
 #include "ctx.h"
 #include "canon.h"
+#include "ingest_pipeline.h"
 #include "prefilter.h"
 #include "../../include/drephip.h"
 
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
-#include <mutex>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -133,7 +129,7 @@ static void pend_release(drephip_ctx *ctx);
 // A deferred sketch (drephip_sketch_device_async) owns the sketch scratch and
 // its status check until drephip_sketch_wait: any other sketch call is refused
 // rather than dropping that check or reusing scratch its kernels still read.
-static int refuse_if_pending(drephip_ctx *ctx) {
+int drephip::refuse_if_pending(drephip_ctx *ctx) {
     if (!ctx->pend.active) return DREPHIP_OK;
     set_error("a deferred sketch (drephip_sketch_device_async) is pending: call drephip_sketch_wait first");
     return DREPHIP_ERR_ARG;
@@ -357,45 +353,6 @@ DREPHIP_EXPORT int drephip_fasta_pack(const char *path, int k, uint32_t *codes, 
     return DREPHIP_OK;
 }
 
-// Stage a packed genome set (already laid out on the host) and sketch it.
-static int sketch_packed_host(drephip_ctx *ctx, const uint32_t *codes, uint64_t n_codes, const uint32_t *valid,
-                              uint64_t n_valid, const std::vector<uint64_t> &off, const std::vector<uint64_t> &pad,
-                              const std::vector<uint64_t> &nk, uint64_t *hashes_out, uint32_t *nhash_out) {
-    const uint32_t n = (uint32_t)off.size();
-    hipStream_t st = ctx->stream;
-    uint32_t *d_codes, *d_valid, *d_nhash;
-    uint64_t *d_hashes;
-    int rc;
-    if ((rc = refuse_if_pending(ctx))) return rc;
-    if ((rc = scratch(ctx, "in_codes", n_codes * 4, (void **)&d_codes))) return rc;
-    if ((rc = scratch(ctx, "in_valid", n_valid * 4, (void **)&d_valid))) return rc;
-    if ((rc = scratch(ctx, "out_hashes", (uint64_t)n * ctx->s * 8, (void **)&d_hashes))) return rc;
-    if ((rc = scratch(ctx, "out_nhash", n * 4ull, (void **)&d_nhash))) return rc;
-    HIPC(hipMemcpyAsync(d_codes, codes, n_codes * 4, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(d_valid, valid, n_valid * 4, hipMemcpyHostToDevice, st));
-    timing_begin(ctx);
-    rc = sketch_device_impl(ctx, d_codes, d_valid, off.data(), pad.data(), nk.data(), n, d_hashes, d_nhash, st);
-    if (rc) return rc;
-    timing_collect(ctx);
-    HIPC(hipMemcpyAsync(hashes_out, d_hashes, (uint64_t)n * ctx->s * 8, hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(nhash_out, d_nhash, n * 4ull, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return DREPHIP_OK;
-}
-
-template <class F>
-static void parallel_for(uint32_t n, int threads, F fn) {
-    int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
-    nt = std::max(1, std::min<int>(nt, (int)n));
-    std::atomic<uint32_t> next(0);
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; t++)
-        pool.emplace_back([&] {
-            for (uint32_t i = next++; i < n; i = next++) fn(i);
-        });
-    for (auto &th : pool) th.join();
-}
-
 DREPHIP_EXPORT int drephip_sketch(drephip_ctx *ctx, const uint8_t *seq, const uint64_t *rec_off,
                                   uint32_t n_rec, const uint64_t *genome_rec_off, uint32_t n_genomes,
                                   uint64_t *hashes_out, uint32_t *nhash_out, uint64_t *length_out) {
@@ -424,7 +381,7 @@ DREPHIP_EXPORT int drephip_sketch(drephip_ctx *ctx, const uint8_t *seq, const ui
         if (length_out) length_out[g] = L;
     }
     std::vector<uint32_t> codes(cur / 16, 0), valid(cur / 32, 0);
-    parallel_for(n_genomes, 0, [&](uint32_t g) {
+    worker_pool(n_genomes, 0, [&](uint32_t, uint32_t g) {
         const uint64_t r0 = genome_rec_off[g], r1 = genome_rec_off[g + 1];
         nk[g] = pack_records(seq + (r1 > r0 ? rec_off[r0] : 0), reclen.data() + r0, (uint32_t)(r1 - r0),
                              ctx->k, codes.data(), valid.data(), off[g]);
@@ -433,472 +390,6 @@ DREPHIP_EXPORT int drephip_sketch(drephip_ctx *ctx, const uint8_t *seq, const ui
                               nhash_out);
 }
 
-// One batch of FASTA files read and packed into pinned host memory.
-struct IngestBatch {
-    uint32_t g0 = 0, n = 0;
-    std::vector<uint64_t> off, pad, nk, length;
-    uint64_t bases = 0;                 // padded positions of the batch (codes/valid span)
-    int err = 0;
-    std::string msg;
-    double seconds = 0;
-    double read_thread_s = 0, pack_thread_s = 0;
-    uint32_t overflow = 0;
-};
-static uint64_t ingest_batch_bases() {
-    if (const char *e = getenv("DREPHIP_INGEST_BATCH_BASES")) {     // tests: force many batches
-        const uint64_t v = strtoull(e, nullptr, 10);
-        if (v) return v;
-    }
-    return 1ull << 30;                  // ~1 Gbase of sequence per batch
-}
-
-// Upper bound on a file's bases (every base is one byte of the uncompressed
-// text): the size of a plain file; for a gzip file its trailer's ISIZE (the
-// uncompressed size mod 2^32 of the LAST member -- exact for the usual
-// single-member file; a multi-member (bgzf) file shows an ISIZE below its
-// compressed size and gets the generic guess of 4x).  A wrong guess costs an
-// overflow repack, never a wrong result.
-static uint64_t estimate_bases(const char *path) {
-    FILE *fp = fopen(path, "rb");
-    if (!fp) return 0;
-    uint8_t magic[2] = {0, 0};
-    const size_t got = fread(magic, 1, 2, fp);
-    fseek(fp, 0, SEEK_END);
-    const long sz = ftell(fp);
-    uint64_t est = sz > 0 ? (uint64_t)sz : 0;
-    if (got == 2 && magic[0] == 0x1f && magic[1] == 0x8b && sz >= 18) {
-        uint8_t t[4];
-        fseek(fp, -4, SEEK_END);
-        if (fread(t, 1, 4, fp) == 4) {
-            const uint64_t isize = (uint64_t)t[0] | (uint64_t)t[1] << 8 | (uint64_t)t[2] << 16 | (uint64_t)t[3] << 24;
-            est = isize >= (uint64_t)sz ? isize : 4 * (uint64_t)sz;
-        }
-    }
-    fclose(fp);
-    return est;
-}
-
-// Grow a pinned slot keeping its first `keep_c` / `keep_v` words.
-static int grow_pinned(PinnedSlot &slot, size_t cb, size_t vb, size_t keep_c, size_t keep_v) {
-    PinnedSlot n;
-    if (n.reserve(cb, vb)) return -1;
-    memcpy(n.codes, slot.codes, keep_c * 4);
-    memcpy(n.valid, slot.valid, keep_v * 4);
-    std::swap(slot.codes, n.codes); std::swap(slot.codes_bytes, n.codes_bytes);
-    std::swap(slot.valid, n.valid); std::swap(slot.valid_bytes, n.valid_bytes);
-    return 0;                          // n frees the old buffers
-}
-
-// One batch: files [g0, ...) chosen by their estimated bases until the batch
-// holds >= target, each given a tile-aligned region of its estimated padded
-// span; then ONE pass over the batch's files on `threads` workers (dynamic
-// scheduling): a worker reads + parses a file into its own reused buffer and
-// packs it straight into the pinned batch while the sequence is cache-hot (a
-// genome whose real span outgrew its estimate is kept and packed after the
-// pass, at the end of the batch).  Regions are zeroed by their worker; the
-// slack between a genome's padded span and its region stays zero and no tile
-// covers it.
-static void produce_batch(const char *const *paths, uint32_t g0, uint32_t n_genomes, int threads, int k,
-                          uint64_t target, PinnedSlot &slot, IngestBatch &B, int device) {
-    const auto t0 = std::chrono::steady_clock::now();
-    (void)hipSetDevice(device);         // the pinned batch belongs with the context's device
-    B = IngestBatch();
-    B.g0 = g0;
-    std::vector<uint64_t> reserved;
-    uint64_t est_total = 0;
-    uint32_t g1 = g0;
-    while (g1 < n_genomes && (g1 == g0 || est_total < target)) {
-        const uint64_t e = estimate_bases(paths[g1]);
-        reserved.push_back(padded_span(e));
-        est_total += e;
-        g1++;
-    }
-    const uint32_t n = g1 - g0;
-    B.n = n;
-    B.off.resize(n); B.pad.resize(n); B.nk.resize(n); B.length.resize(n);
-    uint64_t cur = kTile;
-    for (uint32_t i = 0; i < n; i++) { B.off[i] = cur; cur += reserved[i]; }
-    if (slot.reserve(cur / 16 * 4, cur / 32 * 4)) {
-        B.err = DREPHIP_ERR_NOMEM; B.msg = "hipHostMalloc of the pinned ingest batch failed"; return;
-    }
-    memset(slot.codes, 0, kTile / 16 * 4);
-    memset(slot.valid, 0, kTile / 32 * 4);
-    std::vector<int> err(n, 0);
-    std::vector<std::string> msg(n);
-    std::vector<Genome> overflow(n);                 // genomes whose span outgrew the estimate (rare)
-    std::vector<char> over(n, 0);
-    std::vector<Genome> work(std::max(1, threads > 0 ? threads : (int)std::thread::hardware_concurrency()));
-    std::atomic<uint32_t> next(0);
-    std::vector<double> t_read(work.size(), 0.0), t_pack(work.size(), 0.0);
-    auto worker = [&](uint32_t w) {
-        Genome &g = work[w];                         // reused: no fresh pages per file
-        for (uint32_t i = next++; i < n; i = next++) {
-            const auto r0 = std::chrono::steady_clock::now();
-            const int rr = read_fasta(paths[g0 + i], g);
-            const auto r1 = std::chrono::steady_clock::now();
-            t_read[w] += std::chrono::duration<double>(r1 - r0).count();
-            if (rr) { err[i] = DREPHIP_ERR_IO; msg[i] = drephip_last_error(); continue; }
-            const uint64_t P = padded_span(genome_span(g.rec_len.data(), (uint32_t)g.rec_len.size()));
-            B.length[i] = g.length;
-            B.pad[i] = P;
-            if (P > reserved[i]) { std::swap(overflow[i], g); over[i] = 1; continue; }
-            memset(slot.codes + B.off[i] / 16, 0, reserved[i] / 16 * 4);
-            memset(slot.valid + B.off[i] / 32, 0, reserved[i] / 32 * 4);
-            B.nk[i] = pack_records(g.seq.data(), g.rec_len.data(), (uint32_t)g.rec_len.size(), k, slot.codes,
-                                   slot.valid, B.off[i]);
-            t_pack[w] += std::chrono::duration<double>(std::chrono::steady_clock::now() - r1).count();
-        }
-    };
-    const uint32_t nt = (uint32_t)std::min<size_t>(work.size(), n);
-    std::vector<std::thread> pool;
-    for (uint32_t w = 1; w < nt; w++) pool.emplace_back(worker, w);
-    worker(0);
-    for (auto &th : pool) th.join();
-    for (uint32_t i = 0; i < n; i++)
-        if (err[i]) { B.err = err[i]; B.msg = msg[i]; return; }
-    for (size_t w = 0; w < work.size(); w++) { B.read_thread_s += t_read[w]; B.pack_thread_s += t_pack[w]; }
-    uint64_t end = cur;
-    for (uint32_t i = 0; i < n; i++) if (over[i]) { end += B.pad[i]; B.overflow++; }
-    if (end > cur) {
-        if (grow_pinned(slot, end / 16 * 4, end / 32 * 4, cur / 16, cur / 32)) {
-            B.err = DREPHIP_ERR_NOMEM; B.msg = "hipHostMalloc of the pinned ingest batch failed"; return;
-        }
-        uint64_t at = cur;
-        for (uint32_t i = 0; i < n; i++) {
-            if (!over[i]) continue;
-            const Genome &g = overflow[i];
-            B.off[i] = at;
-            memset(slot.codes + at / 16, 0, B.pad[i] / 16 * 4);
-            memset(slot.valid + at / 32, 0, B.pad[i] / 32 * 4);
-            B.nk[i] = pack_records(g.seq.data(), g.rec_len.data(), (uint32_t)g.rec_len.size(), k, slot.codes,
-                                   slot.valid, at);
-            at += B.pad[i];
-        }
-    }
-    B.bases = end;
-    B.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
-
-// ------------------------------------------------------------ device ingest
-// One file read and packed by the host code into buffers of its own (the
-// device path's gzip and FASTQ files), at base 0.
-struct HostPacked {
-    std::vector<uint32_t> codes, valid;
-    uint64_t pad = 0, nk = 0, length = 0;
-};
-static int host_pack_file(const char *path, int k, Genome &g, HostPacked &hp, double *t_read, double *t_pack) {
-    const auto r0 = std::chrono::steady_clock::now();
-    const int rr = read_fasta(path, g);
-    const auto r1 = std::chrono::steady_clock::now();
-    *t_read += std::chrono::duration<double>(r1 - r0).count();
-    if (rr) return DREPHIP_ERR_IO;
-    const uint32_t nr = (uint32_t)g.rec_len.size();
-    hp.pad = padded_span(genome_span(g.rec_len.data(), nr));
-    hp.length = g.length;
-    hp.codes.assign(hp.pad / 16, 0);
-    hp.valid.assign(hp.pad / 32, 0);
-    hp.nk = pack_records(g.seq.data(), g.rec_len.data(), nr, k, hp.codes.data(), hp.valid.data(), 0);
-    *t_pack += std::chrono::duration<double>(std::chrono::steady_clock::now() - r1).count();
-    return DREPHIP_OK;
-}
-
-// One batch of the device path: the plain files' bytes in a pinned text
-// buffer (16-byte aligned starts), the gzip files packed by the host code.
-struct TextBatch {
-    uint32_t g0 = 0, n = 0;
-    std::vector<uint64_t> off, reserved;        // region of each file (bases)
-    std::vector<uint64_t> text_beg, text_end;   // plain files: their bytes in the text buffer
-    std::vector<char> host;                     // 1: packed by the host code (hp)
-    std::vector<HostPacked> hp;
-    uint64_t bases = 0, text_bytes = 0, text_span = 0;
-    int err = 0;
-    std::string msg;
-    double seconds = 0, read_thread_s = 0, pack_thread_s = 0;
-};
-
-// One look at a file: its size, whether it is gzip, and the upper bound on its
-// bases that estimate_bases gives (the same rule, from the same open).
-// false: it cannot be opened.
-static bool probe_file(const char *path, uint64_t *size, bool *gz, uint64_t *est) {
-    FILE *fp = fopen(path, "rb");
-    if (!fp) return false;
-    uint8_t magic[2] = {0, 0};
-    const size_t got = fread(magic, 1, 2, fp);
-    fseek(fp, 0, SEEK_END);
-    const long sz = ftell(fp);
-    *size = sz > 0 ? (uint64_t)sz : 0;
-    *gz = got == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-    *est = *size;
-    if (*gz && sz >= 18) {
-        uint8_t t[4];
-        fseek(fp, -4, SEEK_END);
-        if (fread(t, 1, 4, fp) == 4) {
-            const uint64_t isize = (uint64_t)t[0] | (uint64_t)t[1] << 8 | (uint64_t)t[2] << 16 | (uint64_t)t[3] << 24;
-            *est = isize >= (uint64_t)sz ? isize : 4 * (uint64_t)sz;
-        }
-    }
-    fclose(fp);
-    return true;
-}
-
-// The device path's producer: the same choice of files and regions as
-// produce_batch (one probe per file gives its estimate, size and kind); then,
-// on `threads` workers, each plain file's bytes go into the pinned text buffer
-// with one pread, unparsed, and each gzip file through the host reader and
-// packer.  A plain file whose size is no longer the probed one takes the host
-// reader too, which reads it whole.
-static void produce_text_batch(const char *const *paths, uint32_t g0, uint32_t n_genomes, int threads, int k,
-                               uint64_t target, PinnedText &slot, TextBatch &B, int device) {
-    const auto t0 = std::chrono::steady_clock::now();
-    (void)hipSetDevice(device);
-    B = TextBatch();
-    B.g0 = g0;
-    uint64_t est_total = 0, cur = kTile, tcur = 0;
-    uint32_t g1 = g0;
-    while (g1 < n_genomes && (g1 == g0 || est_total < target)) {
-        uint64_t size = 0, est = 0;
-        bool gz = false;
-        if (!probe_file(paths[g1], &size, &gz, &est)) {
-            B.n = g1 - g0 + 1;
-            B.err = DREPHIP_ERR_IO; B.msg = std::string("cannot open ") + paths[g1]; return;
-        }
-        B.reserved.push_back(padded_span(est));
-        B.off.push_back(cur);
-        cur += B.reserved.back();
-        B.host.push_back(gz ? 1 : 0);
-        B.text_beg.push_back(tcur);
-        B.text_end.push_back(gz ? tcur : tcur + size);
-        if (!gz) tcur += round_up(size, 16);
-        est_total += est;
-        g1++;
-    }
-    const uint32_t n = g1 - g0;
-    B.n = n;
-    B.hp.resize(n);
-    B.bases = cur;
-    B.text_span = tcur;
-    if (slot.reserve(std::max<uint64_t>(tcur, 16))) {
-        B.err = DREPHIP_ERR_NOMEM; B.msg = "hipHostMalloc of the pinned text batch failed"; return;
-    }
-    std::vector<int> err(n, 0);
-    std::vector<std::string> msg(n);
-    const uint32_t nw = (uint32_t)std::max(1, threads > 0 ? threads : (int)std::thread::hardware_concurrency());
-    std::vector<Genome> work(nw);
-    std::vector<double> t_read(nw, 0.0), t_pack(nw, 0.0);
-    std::atomic<uint32_t> next(0);
-    auto worker = [&](uint32_t w) {
-        for (uint32_t i = next++; i < n; i = next++) {
-            const char *path = paths[g0 + i];
-            if (!B.host[i]) {
-                const auto r0 = std::chrono::steady_clock::now();
-                const int fd = open(path, O_RDONLY);
-                if (fd < 0) { err[i] = DREPHIP_ERR_IO; msg[i] = std::string("cannot open ") + path; continue; }
-                const uint64_t want = B.text_end[i] - B.text_beg[i];
-                struct stat sb;
-                bool same = fstat(fd, &sb) == 0 && (uint64_t)sb.st_size == want;
-                uint64_t got = 0;
-                bool bad = false;
-                while (same && got < want) {           // one pread, repeated only when it comes back short
-                    const ssize_t r = pread(fd, slot.ptr + B.text_beg[i] + got, want - got, (off_t)got);
-                    if (r < 0) { bad = true; break; }
-                    if (r == 0) { same = false; break; }
-                    got += (uint64_t)r;
-                }
-                close(fd);
-                if (bad) { err[i] = DREPHIP_ERR_IO; msg[i] = std::string("read error in ") + path; continue; }
-                t_read[w] += std::chrono::duration<double>(std::chrono::steady_clock::now() - r0).count();
-                if (same) continue;
-                B.host[i] = 1;                         // the file changed since the probe
-                B.text_end[i] = B.text_beg[i];
-            }
-            const int rc = host_pack_file(path, k, work[w], B.hp[i], &t_read[w], &t_pack[w]);
-            if (rc) { err[i] = rc; msg[i] = drephip_last_error(); }
-        }
-    };
-    const uint32_t nt = std::min(nw, n);
-    std::vector<std::thread> pool;
-    for (uint32_t w = 1; w < nt; w++) pool.emplace_back(worker, w);
-    worker(0);
-    for (auto &th : pool) th.join();
-    for (uint32_t i = 0; i < n; i++)
-        if (err[i]) { B.err = err[i]; B.msg = msg[i]; return; }
-    for (uint32_t w = 0; w < nw; w++) { B.read_thread_s += t_read[w]; B.pack_thread_s += t_pack[w]; }
-    for (uint32_t i = 0; i < n; i++) B.text_bytes += B.text_end[i] - B.text_beg[i];
-    B.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
-
-// The device path's consumer: text to the device, pack kernels, the host
-// reader for the files the kernels hand back, then the device-resident sketch.
-// A host-packed file (gzip, FASTQ, or a defensive status 2) is copied over its
-// region, which is zeroed whole first: the slack behind a genome's padded span
-// is read by the sketch of the genome that follows and must not keep what an
-// earlier batch left in the scratch.  One whose span outgrew its region goes to
-// the end of the batch (its old region zeroed all the same).
-static int consume_text_batch(drephip_ctx *ctx, const char *const *paths, int threads, TextBatch &B,
-                              const PinnedText &slot, uint64_t *hashes_out, uint32_t *nhash_out,
-                              uint64_t *length_out) {
-    const uint32_t n = B.n;
-    hipStream_t st = ctx->stream;
-    std::vector<uint64_t> pad(n, 0), nk(n, 0), length(n, 0), off(B.off);
-    uint32_t moved = 0, device_files = 0, host_files = 0;
-    uint64_t end = B.bases;
-    for (uint32_t i = 0; i < n; i++)
-        if (B.host[i] && B.hp[i].pad > B.reserved[i]) { off[i] = end; end += B.hp[i].pad; moved++; }
-    uint8_t *d_text;
-    uint32_t *d_codes, *d_valid, *d_nhash;
-    uint64_t *d_hashes;
-    int rc;
-    if ((rc = scratch(ctx, "in_text", std::max<uint64_t>(B.text_span, 16), (void **)&d_text))) return rc;
-    if ((rc = scratch(ctx, "in_codes", end / 16 * 4, (void **)&d_codes))) return rc;
-    if ((rc = scratch(ctx, "in_valid", end / 32 * 4, (void **)&d_valid))) return rc;
-    if ((rc = scratch(ctx, "out_hashes", (uint64_t)n * ctx->s * 8, (void **)&d_hashes))) return rc;
-    if ((rc = scratch(ctx, "out_nhash", n * 4ull, (void **)&d_nhash))) return rc;
-    if (B.text_span) HIPC(hipMemcpyAsync(d_text, slot.ptr, B.text_span, hipMemcpyHostToDevice, st));
-    HIPC(hipMemsetAsync(d_codes, 0, kTile / 16 * 4, st));
-    HIPC(hipMemsetAsync(d_valid, 0, kTile / 32 * 4, st));
-    for (uint32_t i = 0; i < n; i++) {                   // the host-packed files' regions (the pack call zeroes the others)
-        if (!B.host[i]) continue;
-        HIPC(hipMemsetAsync(d_codes + B.off[i] / 16, 0, B.reserved[i] / 16 * 4, st));
-        HIPC(hipMemsetAsync(d_valid + B.off[i] / 32, 0, B.reserved[i] / 32 * 4, st));
-    }
-    std::vector<uint32_t> dev;                           // the plain files
-    for (uint32_t i = 0; i < n; i++) if (!B.host[i]) dev.push_back(i);
-    std::vector<uint32_t> back;                          // handed back to the host reader
-    if (!dev.empty()) {
-        const uint32_t m = (uint32_t)dev.size();
-        std::vector<uint64_t> tb(m), te(m), bo(m), cp(m), ln(m), pd(m), kk(m);
-        std::vector<uint32_t> nr(m);
-        std::vector<uint8_t> stt(m);
-        for (uint32_t j = 0; j < m; j++) {
-            tb[j] = B.text_beg[dev[j]]; te[j] = B.text_end[dev[j]];
-            bo[j] = B.off[dev[j]]; cp[j] = B.reserved[dev[j]];
-        }
-        rc = fasta_pack_device_impl(ctx, d_text, tb.data(), te.data(), m, bo.data(), cp.data(), d_codes, d_valid, ln.data(),
-                                    pd.data(), nr.data(), kk.data(), stt.data(), st);
-        if (rc) return rc;
-        for (uint32_t j = 0; j < m; j++) {
-            const uint32_t i = dev[j];
-            if (stt[j] == 0) { length[i] = ln[j]; pad[i] = pd[j]; nk[i] = kk[j]; device_files++; }
-            else back.push_back(i);
-        }
-    }
-    if (!back.empty()) {
-        std::vector<int> err(back.size(), 0);
-        std::vector<std::string> msg(back.size());
-        std::vector<double> tr(back.size(), 0.0), tp(back.size(), 0.0);
-        parallel_for((uint32_t)back.size(), threads, [&](uint32_t j) {
-            Genome g;
-            err[j] = host_pack_file(paths[B.g0 + back[j]], ctx->k, g, B.hp[back[j]], &tr[j], &tp[j]);
-            if (err[j]) msg[j] = drephip_last_error();
-        });
-        bool again = false;
-        for (size_t j = 0; j < back.size(); j++) {
-            if (err[j]) { set_error(msg[j]); return err[j]; }
-            ctx->ingest.read_thread_s += tr[j];
-            ctx->ingest.pack_thread_s += tp[j];
-            B.host[back[j]] = 1;
-            again |= B.hp[back[j]].pad > B.reserved[back[j]];
-        }
-        // A handed-back file that outgrew its region needs room behind the batch, as
-        // a gzip file does: start over with it among the host-packed files (the
-        // buffers may move).  A plain file's span never exceeds its size's, so
-        // this is a defence only.
-        if (again) return consume_text_batch(ctx, paths, threads, B, slot, hashes_out, nhash_out, length_out);
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        if (!B.host[i]) continue;
-        const HostPacked &hp = B.hp[i];
-        HIPC(hipMemcpyAsync(d_codes + off[i] / 16, hp.codes.data(), hp.pad / 16 * 4, hipMemcpyHostToDevice, st));
-        HIPC(hipMemcpyAsync(d_valid + off[i] / 32, hp.valid.data(), hp.pad / 32 * 4, hipMemcpyHostToDevice, st));
-        length[i] = hp.length; pad[i] = hp.pad; nk[i] = hp.nk;
-        host_files++;
-    }
-    if (length_out) std::copy(length.begin(), length.end(), length_out + B.g0);
-    timing_begin(ctx);
-    rc = sketch_device_impl(ctx, d_codes, d_valid, off.data(), pad.data(), nk.data(), n, d_hashes, d_nhash, st);
-    if (rc) return rc;
-    timing_collect(ctx);
-    HIPC(hipMemcpyAsync(hashes_out + (uint64_t)B.g0 * ctx->s, d_hashes, (uint64_t)n * ctx->s * 8, hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(nhash_out + B.g0, d_nhash, n * 4ull, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    ctx->ingest_paths.text_bytes += B.text_bytes;
-    ctx->ingest_paths.device_files += device_files;
-    ctx->ingest_paths.host_files += host_files;
-    ctx->ingest.overflow += moved;
-    return DREPHIP_OK;
-}
-
-// drephip_sketch_files on the device path: the same double-buffered producer /
-// consumer as the host path below, over text batches.
-static int sketch_files_device(drephip_ctx *ctx, const char *const *paths, uint32_t n_genomes, int threads,
-                               uint64_t *hashes_out, uint32_t *nhash_out, uint64_t *length_out) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t target = ingest_batch_bases();
-    PinnedText *slots = ctx->ingest_text;
-    TextBatch B[2];
-    const int k = ctx->k;
-    std::mutex mu;
-    std::condition_variable cv;
-    uint32_t produced = 0, consumed = 0;
-    bool stop = false;
-    std::thread producer([&] {
-        uint32_t g = 0;
-        for (uint32_t i = 0; g < n_genomes; i++) {
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || consumed + 2 > i; });
-                if (stop) return;
-            }
-            produce_text_batch(paths, g, n_genomes, threads, k, target, slots[i & 1], B[i & 1], ctx->device);
-            const bool last = B[i & 1].err || g + B[i & 1].n >= n_genomes;
-            g += B[i & 1].n;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                produced = i + 1;
-            }
-            cv.notify_all();
-            if (last) return;
-        }
-    });
-    int rc = DREPHIP_OK;
-    for (uint32_t b = 0;; b++) {
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return produced > b; });
-        }
-        TextBatch &cur = B[b & 1];
-        if (cur.err) { set_error(cur.msg); rc = cur.err; break; }
-        const bool more = cur.g0 + cur.n < n_genomes;
-        const auto g0 = std::chrono::steady_clock::now();
-        rc = consume_text_batch(ctx, paths, threads, cur, slots[b & 1], hashes_out, nhash_out, length_out);
-        ctx->ingest.gpu_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - g0).count();
-        ctx->ingest.produce_s += cur.seconds;
-        ctx->ingest.read_thread_s += cur.read_thread_s;
-        ctx->ingest.pack_thread_s += cur.pack_thread_s;
-        ctx->ingest.batches++;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            consumed = b + 1;
-        }
-        cv.notify_all();
-        if (rc || !more) break;
-    }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        stop = true;
-    }
-    cv.notify_all();
-    producer.join();
-    ctx->ingest.wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
-}
-
-// Ingest pipeline: one producer thread reads + packs batch i+1 (on `threads`
-// workers, into the other of two pinned buffers) while this thread copies
-// batch i to the GPU and sketches it -- the GPU work hides behind the host
-// ingest, which is the slower side by an order of magnitude.  The producer
-// lives for the whole call (a thread per batch paid the HIP runtime's
-// per-thread setup and teardown, ~30 ms, on every batch).
 DREPHIP_EXPORT int drephip_sketch_files(drephip_ctx *ctx, const char *const *paths, uint32_t n_genomes,
                                         int threads, uint64_t *hashes_out, uint32_t *nhash_out,
                                         uint64_t *length_out) {
@@ -909,71 +400,7 @@ DREPHIP_EXPORT int drephip_sketch_files(drephip_ctx *ctx, const char *const *pat
     if (!paths || !hashes_out || !nhash_out) { set_error("null argument"); return DREPHIP_ERR_ARG; }
     int rc;
     if ((rc = refuse_if_pending(ctx))) return rc;
-    if (ctx->ingest_path == DREPHIP_INGEST_DEVICE)
-        return sketch_files_device(ctx, paths, n_genomes, threads, hashes_out, nhash_out, length_out);
-    ctx->ingest_paths.host_files = n_genomes;
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t target = ingest_batch_bases();
-    PinnedSlot *slots = ctx->ingest_slots;          // kept across calls: pinned allocation is slow
-    IngestBatch B[2];
-    const int k = ctx->k;
-    std::mutex mu;
-    std::condition_variable cv;
-    uint32_t produced = 0, consumed = 0;            // batches handed over / released
-    bool stop = false;
-    std::thread producer([&] {
-        uint32_t g = 0;
-        for (uint32_t i = 0; g < n_genomes; i++) {
-            {   // slot i & 1 is free once batch i - 2 has been consumed
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || consumed + 2 > i; });
-                if (stop) return;
-            }
-            produce_batch(paths, g, n_genomes, threads, k, target, slots[i & 1], B[i & 1], ctx->device);
-            const bool last = B[i & 1].err || g + B[i & 1].n >= n_genomes;
-            g += B[i & 1].n;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                produced = i + 1;
-            }
-            cv.notify_all();
-            if (last) return;
-        }
-    });
-    rc = DREPHIP_OK;
-    for (uint32_t b = 0;; b++) {
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return produced > b; });
-        }
-        IngestBatch &cur = B[b & 1];
-        if (cur.err) { set_error(cur.msg); rc = cur.err; break; }
-        const bool more = cur.g0 + cur.n < n_genomes;
-        const auto g0 = std::chrono::steady_clock::now();
-        if (length_out) std::copy(cur.length.begin(), cur.length.end(), length_out + cur.g0);
-        rc = sketch_packed_host(ctx, slots[b & 1].codes, cur.bases / 16, slots[b & 1].valid, cur.bases / 32, cur.off,
-                                cur.pad, cur.nk, hashes_out + (uint64_t)cur.g0 * ctx->s, nhash_out + cur.g0);
-        ctx->ingest.gpu_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - g0).count();
-        ctx->ingest.produce_s += cur.seconds;
-        ctx->ingest.read_thread_s += cur.read_thread_s;
-        ctx->ingest.pack_thread_s += cur.pack_thread_s;
-        ctx->ingest.overflow += cur.overflow;
-        ctx->ingest.batches++;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            consumed = b + 1;
-        }
-        cv.notify_all();
-        if (rc || !more) break;
-    }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        stop = true;                                // a producer waiting for a slot ends
-    }
-    cv.notify_all();
-    producer.join();
-    ctx->ingest.wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    return sketch_files_impl(ctx, paths, n_genomes, threads, hashes_out, nhash_out, length_out);
 }
 
 DREPHIP_EXPORT int drephip_last_ingest_stats(drephip_ctx *ctx, double *produce_s, double *gpu_s, double *wall_s,

@@ -450,6 +450,19 @@ int fasta_pack_device_impl(drephip_ctx *ctx, const uint8_t *d_text, const uint64
                            uint64_t *length_out, uint64_t *padded_out, uint32_t *n_records_out, uint64_t *n_kmers_out,
                            uint8_t *status_out, hipStream_t st);
 
+// The file ingest (ingest_pipeline.cpp).  refuse_if_pending (api.cpp): an error
+// while a deferred sketch owns the sketch scratch.  sketch_packed_host: a
+// packed genome set laid out on the host (genome g at bases [off[g], off[g] +
+// pad[g]) of codes / valid) staged and sketched, the sketches brought back to
+// the host.  sketch_files_impl: the body of drephip_sketch_files after its
+// argument checks.  Both block.
+int refuse_if_pending(drephip_ctx *ctx);
+int sketch_packed_host(drephip_ctx *ctx, const uint32_t *codes, uint64_t n_codes, const uint32_t *valid,
+                       uint64_t n_valid, const std::vector<uint64_t> &off, const std::vector<uint64_t> &pad,
+                       const std::vector<uint64_t> &nk, uint64_t *hashes_out, uint32_t *nhash_out);
+int sketch_files_impl(drephip_ctx *ctx, const char *const *paths, uint32_t n_genomes, int threads,
+                      uint64_t *hashes_out, uint32_t *nhash_out, uint64_t *length_out);
+
 // Host ingest (ingest.cpp).
 // std::allocator that leaves new elements uninitialised (resize() without the
 // memset: the FASTA reader writes every byte it keeps)

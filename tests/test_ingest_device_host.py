@@ -41,22 +41,53 @@ def test_ingest_kwarg_is_checked_on_a_dry_run(tmp_path):
         d_cluster.all_vs_all_MASH(Bdb, str(tmp_path), dry=True, ingest="gpu")
 
 
+def _host_program(tmp_path, source, name, sanitize, libs=()):
+    """`source` built as a stand-alone host program with -fsanitize=`sanitize`."""
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    exe = tmp_path / name
+    subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g",
+                    "-fsanitize=" + sanitize, "-fno-sanitize-recover=undefined",
+                    "-I", os.path.join(ROOT, "drep_amd", "csrc"), str(source), "-o", str(exe), *libs],
+                   check=True, capture_output=True, cwd=tmp_path)
+    return exe
+
+
 def test_byte_machine_and_tile_lists_on_the_host(tmp_path):
     """tools/fasta_machine_check.cpp: the kernels' lane / tile decomposition, the
     pack call's tile and chunk lists and the kernels' search in them, replayed
     on the CPU through the inline functions the kernels call
     (csrc/fasta_machine.h), as a stand-alone host program built with the
     address and undefined-behaviour sanitizers."""
-    import shutil
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    exe = tmp_path / "fasta_machine_check"
-    subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", os.path.join(ROOT, "drep_amd", "csrc"),
-                    os.path.join(ROOT, "tools", "fasta_machine_check.cpp"), "-o", str(exe)],
-                   check=True, capture_output=True, cwd=tmp_path)
+    exe = _host_program(tmp_path, os.path.join(ROOT, "tools", "fasta_machine_check.cpp"), "fasta_machine_check",
+                        "address,undefined")
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert ", 0 disagree" in out.stdout and not out.stderr.strip(), out.stdout + out.stderr
+
+
+@pytest.mark.parametrize("sanitize", ["address,undefined", "thread"])
+def test_ingest_pipeline_machinery_on_the_host(tmp_path, sanitize):
+    """tools/ingest_pipeline_check.cpp: the producer / consumer driver of
+    drephip_sketch_files under fake stages (order, slot ownership, an error on
+    either side with the other parked or mid-batch), its batch plan and its
+    worker pool (csrc/ingest_pipeline.h), as a stand-alone host program: once
+    with the address and undefined-behaviour sanitizers, once with the thread
+    sanitizer."""
+    if sanitize == "thread":
+        # skipped only where the thread sanitizer's runtime itself cannot start
+        trivial = tmp_path / "trivial.cpp"
+        trivial.write_text("#include <thread>\nint main() { int x = 0; std::thread t([&] { x = 1; }); t.join();\n"
+                           "  return x - 1; }\n")
+        probe = subprocess.run([str(_host_program(tmp_path, trivial, "trivial", sanitize))], capture_output=True,
+                               text=True, timeout=60)
+        if probe.returncode != 0:
+            pytest.skip("a three-line program built with -fsanitize=thread cannot start here (the runtime refuses "
+                        "the address layout): " + probe.stderr.strip()[:200])
+    exe = _host_program(tmp_path, os.path.join(ROOT, "tools", "ingest_pipeline_check.cpp"), "ingest_pipeline_check",
+                        sanitize, libs=["-lz"])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
     assert ", 0 disagree" in out.stdout and not out.stderr.strip(), out.stdout + out.stderr
