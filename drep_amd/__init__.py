@@ -14,7 +14,8 @@ from ._lib import Context, DrepHipError
 __all__ = ["Context", "DrepHipError", "mash_io", "d_cluster", "SparseMash", "all_vs_all_MASH_sparse",
            "cluster_mash_sparse", "mdb_from_sparse", "store_sparse", "load_sparse", "RectMash", "query_vs_MASH",
            "query_vs_MASH_rect", "rect_allpairs", "rect_allpairs_sparse", "mdb_from_rect", "union_condensed",
-           "rect_top_hits", "query_best_hits", "place_queries"]
+           "rect_top_hits", "query_best_hits", "place_queries", "mash_pvalue_device", "min_common_table",
+           "write_mash_table_rect", "sparse_allpairs_sig", "rect_allpairs_sparse_sig"]
 __version__ = "0.1.0"
 
 
@@ -28,6 +29,10 @@ def __getattr__(name):
     if name in ("RectMash", "query_vs_MASH", "query_vs_MASH_rect", "rect_allpairs", "rect_allpairs_sparse",
                 "mdb_from_rect", "union_condensed", "rect_top_hits", "query_best_hits", "place_queries"):
         import importlib           # query against reference (`mash dist <reference> <query>`)
+        return getattr(importlib.import_module(".d_cluster", __name__), name)
+    if name in ("mash_pvalue_device", "min_common_table", "write_mash_table_rect", "sparse_allpairs_sig",
+                "rect_allpairs_sparse_sig"):
+        import importlib           # significance: Mash's p-value and its -v / -d filters on the GPU
         return getattr(importlib.import_module(".d_cluster", __name__), name)
     if name in ("store_sparse", "load_sparse"):
         import importlib

@@ -108,6 +108,19 @@ SIGNATURES = {
                                                C.c_uint32, vp, vp, vp]),
     "drephip_dist_rect_top": (C.c_int, [vp, u64p, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                         C.c_uint32, vp, vp]),
+    "drephip_pvalue_eval": (C.c_int, [C.c_int, C.c_uint32, u32p, u64p, u64p, C.c_uint64, f64p, vp, vp]),
+    "drephip_pvalue_records_device": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, vp, vp]),
+    "drephip_pvalue_records": (C.c_int, [vp, vp, C.c_uint64, u64p, C.c_uint32, u64p, C.c_uint32, vp]),
+    "drephip_pvalue_hits_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, vp]),
+    "drephip_records_filter_device": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_double, vp, vp, vp,
+                                                C.POINTER(C.c_uint64), vp]),
+    "drephip_allpairs_sparse_sig": (C.c_int, [vp, u64p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_double,
+                                              vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "drephip_dist_rect_sparse_sig": (C.c_int, [vp, u64p, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint32,
+                                               C.c_uint32, u64p, u64p, C.c_double, vp, vp, C.c_uint64, vp,
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "drephip_write_mash_table_rect": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p),
+                                                C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_int]),
     "drephip_last_sparse_stats": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint64)]),
     "drephip_distance_lut": (C.c_int, [C.c_int, C.c_uint32, f64p]),
@@ -328,6 +341,71 @@ def write_mash_table(path: str, names: Sequence[str], common: np.ndarray, denom:
                                          pval.ctypes.data, np.ascontiguousarray(self_count, dtype=np.uint16),
                                          np.ascontiguousarray(self_pval, dtype=np.float64), int(threads)),
           "drephip_write_mash_table(%s)" % path)
+
+
+def write_mash_table_rect(path: str, rnames: Sequence[str], qnames: Sequence[str], common: np.ndarray,
+                          denom: Optional[np.ndarray], s: int, dist: np.ndarray, pval: np.ndarray,
+                          threads: int = 0) -> None:
+    """drephip_write_mash_table_rect: the [Q, N] rectangle's arrays (row-major,
+    query rows), names of the N references and the Q queries."""
+    N, Q = len(rnames), len(qnames)
+    common = np.ascontiguousarray(common, dtype=np.uint16)
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    pval = np.ascontiguousarray(pval, dtype=np.float64)
+    den = None if denom is None else np.ascontiguousarray(denom, dtype=np.uint16)
+    for a in (common, dist, pval) + ((den,) if den is not None else ()):
+        if a.size != Q * N:
+            raise ValueError("rectangle arrays must hold Q x N = %d entries" % (Q * N))
+    ra = (C.c_char_p * max(N, 1))(*[os.fsencode(n) for n in rnames])
+    qa = (C.c_char_p * max(Q, 1))(*[os.fsencode(n) for n in qnames])
+    check(lib().drephip_write_mash_table_rect(os.fsencode(path), ra, N, qa, Q, common.ctypes.data,
+                                              None if den is None else den.ctypes.data, int(s), dist.ctypes.data,
+                                              pval.ctypes.data, int(threads)),
+          "drephip_write_mash_table_rect(%s)" % path)
+
+
+def pvalue_eval(common: np.ndarray, len_a: np.ndarray, len_b: np.ndarray, s: int, k: int = 21,
+                want_rn: bool = False):
+    """drephip_pvalue_eval (host, no GPU): Mash's p-value of each (common,
+    len_a, len_b) at sketch size s and k-mer size k, through the inline
+    functions the kernels call (drep_amd/csrc/pvalue.h).  want_rn: also the
+    binomial's r (float64) and n (uint32) of every pair."""
+    common = np.ascontiguousarray(common, dtype=np.uint32)
+    len_a = np.ascontiguousarray(len_a, dtype=np.uint64)
+    len_b = np.ascontiguousarray(len_b, dtype=np.uint64)
+    if not (common.ndim == 1 and common.shape == len_a.shape == len_b.shape):
+        raise ValueError("common, len_a and len_b must be equal-length vectors")
+    n = len(common)
+    m = max(n, 1)
+    p = np.zeros(m, np.float64)
+    r = np.zeros(m, np.float64) if want_rn else None
+    nn = np.zeros(m, np.uint32) if want_rn else None
+    z32, z64 = np.zeros(1, np.uint32), np.zeros(1, np.uint64)
+    check(lib().drephip_pvalue_eval(int(k), int(s), common if n else z32, len_a if n else z64, len_b if n else z64,
+                                    n, p, _ptr(r), _ptr(nn)), "drephip_pvalue_eval")
+    return (p[:n], r[:n], nn[:n]) if want_rn else p[:n]
+
+
+def _records(records: np.ndarray) -> np.ndarray:
+    records = np.ascontiguousarray(records, dtype=np.uint32)
+    if records.ndim != 2 or records.shape[1] != 4:
+        raise ValueError("records must be a uint32 [n, 4] array")
+    return records
+
+
+def _lengths(length, n: int) -> np.ndarray:
+    length = np.ascontiguousarray(length, dtype=np.uint64)
+    if length.shape != (n,):
+        raise ValueError("lengths must hold one entry per sketch row (%d), got %s" % (n, length.shape))
+    return length
+
+
+def _sorted_sig(rec: np.ndarray, pv: np.ndarray):
+    """Records and their p-values sorted by (first, second) index, as columns."""
+    order = np.lexsort((rec[:, 1], rec[:, 0]))
+    rec = rec[order]
+    return (np.ascontiguousarray(rec[:, 0]), np.ascontiguousarray(rec[:, 1]), rec[:, 2].astype(np.uint16),
+            rec[:, 3].astype(np.uint16), np.ascontiguousarray(pv[order]))
 
 
 def fasta_info(path: str, k: int = 21):
@@ -1024,6 +1102,219 @@ class Context:
         d_count uint32 [q1 - q0], device pointers."""
         check(lib().drephip_dist_rect_top_device(self._h, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1,
                                                  int(top), d_hits, d_count, stream), "drephip_dist_rect_top_device")
+
+    # -- significance (include/drephip.h: drephip_pvalue_records ...)
+    def pvalue_records(self, records: np.ndarray, len_a: np.ndarray, len_b: Optional[np.ndarray] = None,
+                       out: Optional[np.ndarray] = None) -> np.ndarray:
+        """drephip_pvalue_records: Mash's p-value of each record {a, b, common,
+        denom} (uint32 [n, 4]) on the GPU; a indexes len_a, b indexes len_b
+        (default: len_a, the triangle's records).  `out`: a contiguous float64
+        buffer of at least n entries to write into."""
+        records = _records(records)
+        len_a = np.ascontiguousarray(len_a, dtype=np.uint64)
+        len_b = len_a if len_b is None else np.ascontiguousarray(len_b, dtype=np.uint64)
+        n = len(records)
+        if out is None:
+            out = np.empty(n, dtype=np.float64)
+        elif out.dtype != np.float64 or not out.flags.c_contiguous or out.size < n:
+            raise ValueError("out must be contiguous float64 of at least %d entries" % n)
+        z = np.zeros(1, np.uint64)
+        check(lib().drephip_pvalue_records(self._h, records.ctypes.data, n, len_a if len(len_a) else z, len(len_a),
+                                           len_b if len(len_b) else z, len(len_b), out.ctypes.data),
+              "drephip_pvalue_records")
+        return out[:n]
+
+    def pvalue_records_device(self, d_records: Optional[int], n: int, d_len_a: Optional[int], n_a: int,
+                              d_len_b: Optional[int], n_b: int, d_pval: Optional[int],
+                              stream: Optional[int] = None) -> None:
+        """drephip_pvalue_records_device: device pointers (records uint32 [n, 4],
+        lengths uint64, d_pval float64 [n])."""
+        check(lib().drephip_pvalue_records_device(self._h, d_records, int(n), d_len_a, int(n_a), d_len_b, int(n_b),
+                                                  d_pval, stream), "drephip_pvalue_records_device")
+
+    def pvalue_hits_device(self, d_hits: Optional[int], d_count: Optional[int], rows: int, top: int,
+                           d_qlen: Optional[int], d_rlen: Optional[int], N: int, d_pval: Optional[int],
+                           stream: Optional[int] = None) -> None:
+        """drephip_pvalue_hits_device: device pointers (the hits and counts of
+        dist_rect_top_device, uint64 lengths, d_pval float64 [rows, top])."""
+        check(lib().drephip_pvalue_hits_device(self._h, d_hits, d_count, int(rows), int(top), d_qlen, d_rlen, int(N),
+                                               d_pval, stream), "drephip_pvalue_hits_device")
+
+    def _torch_dev(self):
+        import torch
+        return torch, torch.device("cuda", self.device)
+
+    def pvalue_hits(self, ref: np.ndarray, common: np.ndarray, denom: np.ndarray, count: np.ndarray,
+                    qlen: np.ndarray, rlen: np.ndarray) -> np.ndarray:
+        """The p-values of the best hits dist_rect_top returned ((ref, common,
+        denom) [rows, top], count [rows]; qlen: the rows' query lengths, rlen:
+        every reference's): float64 [rows, top], 1.0 in the slots at or past
+        count[row].  Staged with torch on this context's device
+        (drephip_pvalue_hits_device)."""
+        ref = np.asarray(ref)
+        rows, top = ref.shape
+        hits = np.zeros((rows, top, 4), dtype=np.uint32)
+        hits[:, :, 0] = np.where(ref < 0, 0xFFFFFFFF, ref).astype(np.uint32)
+        hits[:, :, 1] = common
+        hits[:, :, 2] = denom
+        qlen = np.ascontiguousarray(qlen, dtype=np.uint64)
+        rlen = np.ascontiguousarray(rlen, dtype=np.uint64)
+        if len(qlen) != rows:
+            raise ValueError("qlen must hold one length per row")
+        if rows == 0 or top == 0:
+            return np.ones((rows, top), dtype=np.float64)
+        torch, dev = self._torch_dev()
+        with torch.cuda.device(dev):
+            d_h = torch.tensor(hits.view(np.int32), device=dev)
+            d_c = torch.tensor(np.ascontiguousarray(count, dtype=np.uint32).view(np.int32), device=dev)
+            d_q = torch.tensor(qlen.view(np.int64), device=dev)
+            d_r = torch.tensor(rlen.view(np.int64) if len(rlen) else np.zeros(1, np.int64), device=dev)
+            d_p = torch.zeros((rows, top), dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)
+            self.pvalue_hits_device(d_h.data_ptr(), d_c.data_ptr(), rows, top, d_q.data_ptr(), d_r.data_ptr(),
+                                    len(rlen), d_p.data_ptr())
+            return d_p.cpu().numpy()
+
+    def filter_records_device(self, d_records: Optional[int], d_pval: Optional[int], n: int, max_p: float,
+                              d_cmin: Optional[int], d_out: Optional[int], d_pval_out: Optional[int],
+                              stream: Optional[int] = None) -> int:
+        """drephip_records_filter_device (device pointers): the survivors' count."""
+        kept = C.c_uint64(0)
+        check(lib().drephip_records_filter_device(self._h, d_records, d_pval, int(n), float(max_p), d_cmin, d_out,
+                                                  d_pval_out, C.byref(kept), stream), "drephip_records_filter_device")
+        return int(kept.value)
+
+    def filter_records(self, records: np.ndarray, pval: Optional[np.ndarray] = None, max_p: float = 1.0,
+                       cmin: Optional[np.ndarray] = None):
+        """The records (uint32 [n, 4]) with pval <= max_p (no test without
+        pval) and common >= cmin[denom] (cmin: s + 1 entries, see
+        d_cluster.min_common_table; no test without it), in their order:
+        (records, pval or None).  Staged with torch on this context's device
+        (drephip_records_filter_device)."""
+        records = _records(records)
+        n = len(records)
+        if pval is not None:
+            pval = np.ascontiguousarray(pval, dtype=np.float64)
+            if pval.shape != (n,):
+                raise ValueError("pval must hold one value per record")
+        if cmin is not None:
+            cmin = np.ascontiguousarray(cmin, dtype=np.uint32)
+            if cmin.shape != (self.s + 1,):
+                raise ValueError("cmin must hold s + 1 entries")
+        torch, dev = self._torch_dev()
+        with torch.cuda.device(dev):
+            d_r = torch.tensor(records.view(np.int32) if n else np.zeros((1, 4), np.int32), device=dev)
+            d_p = None if pval is None else torch.tensor(pval if n else np.zeros(1), device=dev)
+            d_c = None if cmin is None else torch.tensor(cmin.view(np.int32), device=dev)
+            d_o = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=dev)
+            d_po = None if pval is None else torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)
+            kept = self.filter_records_device(d_r.data_ptr(), None if d_p is None else d_p.data_ptr(), n, max_p,
+                                              None if d_c is None else d_c.data_ptr(), d_o.data_ptr(),
+                                              None if d_po is None else d_po.data_ptr())
+            out = d_o[:kept].cpu().numpy().view(np.uint32)
+            return out, (None if d_po is None else d_po[:kept].cpu().numpy())
+
+    def _sig_call(self, call, what: str, n_first: int, length_arrays, max_p: float, cmin, cap: Optional[int],
+                  want_pval: bool):
+        """One _sig host call with the retry of the record calls: (records
+        uint32 [n, 4] in the device call's order, pval or None, n_listed)."""
+        if cmin is not None:
+            cmin = np.ascontiguousarray(cmin, dtype=np.uint32)
+            if cmin.shape != (self.s + 1,):
+                raise ValueError("cmin must hold s + 1 entries")
+        cap = int(cap) if cap is not None else 8 * n_first + 4096
+        n, listed = C.c_uint64(0), C.c_uint64(0)
+        for _ in range(2):
+            buf = np.empty((max(cap, 1), 4), dtype=np.uint32)
+            pv = np.empty(max(cap, 1), dtype=np.float64) if want_pval else None
+            rc = call(*length_arrays, float(max_p), _ptr(cmin), buf.ctypes.data if cap else None, cap, _ptr(pv),
+                      C.byref(n), C.byref(listed))
+            if rc != self.ERR_NOMEM:
+                break
+            cap = n.value
+        check(rc, what)
+        return buf[:n.value], (None if pv is None else pv[:n.value]), int(listed.value)
+
+    def allpairs_sparse_sig_raw(self, hashes: np.ndarray, nhash: np.ndarray, length: np.ndarray, row0: int, row1: int,
+                                max_p: float, cmin: Optional[np.ndarray], pairs: Optional[np.ndarray],
+                                pval: Optional[np.ndarray]) -> Tuple[int, int, int]:
+        """One drephip_allpairs_sparse_sig call into `pairs` (uint32 [cap, 4];
+        None: count only) and `pval` (float64 [cap] or None): (return code,
+        records that pass the filter, records listed before it).  Raises on
+        every error but DREPHIP_ERR_NOMEM."""
+        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+        nhash = np.ascontiguousarray(nhash, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.uint64)
+        N = len(nhash)
+        if hashes.shape != (N, self.s) or length.shape != (N,):
+            raise ValueError("hashes must be [N, s] and length [N]")
+        cap = 0 if pairs is None else len(pairs)
+        cm = None if cmin is None else np.ascontiguousarray(cmin, dtype=np.uint32)
+        n, listed = C.c_uint64(0), C.c_uint64(0)
+        rc = lib().drephip_allpairs_sparse_sig(self._h, hashes.reshape(-1), nhash, N, int(row0), int(row1), length,
+                                               float(max_p), _ptr(cm), pairs.ctypes.data if cap else None, cap,
+                                               _ptr(pval), C.byref(n), C.byref(listed))
+        if rc != self.ERR_NOMEM:
+            check(rc, "drephip_allpairs_sparse_sig")
+        return rc, n.value, listed.value
+
+    def allpairs_sparse_sig(self, hashes: np.ndarray, nhash: np.ndarray, length: np.ndarray, max_p: float = 1.0,
+                            cmin: Optional[np.ndarray] = None, row0: int = 0, row1: Optional[int] = None,
+                            cap: Optional[int] = None):
+        """allpairs_sparse with Mash's p-value per record and the -v / -d
+        filters applied on the GPU before the copy
+        (drephip_allpairs_sparse_sig): (i, j, common, denom, p, n_listed), the
+        records sorted by (i, j); n_listed counts them before the filter."""
+        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+        nhash = np.ascontiguousarray(nhash, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.uint64)
+        N = len(nhash)
+        if hashes.shape != (N, self.s) or length.shape != (N,):
+            raise ValueError("hashes must be [N, s] and length [N]")
+        row1 = N if row1 is None else int(row1)
+
+        def call(ln, *rest):
+            return lib().drephip_allpairs_sparse_sig(self._h, hashes.reshape(-1), nhash, N, int(row0), row1, ln, *rest)
+        rec, pv, listed = self._sig_call(call, "drephip_allpairs_sparse_sig", N, (length,), max_p, cmin, cap, True)
+        return _sorted_sig(rec, pv) + (listed,)
+
+    def dist_rect_sparse_sig_raw(self, qhashes, qnhash, rhashes, rnhash, qlength, rlength, q0: int, q1: Optional[int],
+                                 max_p: float, cmin: Optional[np.ndarray], pairs: Optional[np.ndarray],
+                                 pval: Optional[np.ndarray]) -> Tuple[int, int, int]:
+        """One drephip_dist_rect_sparse_sig call (see allpairs_sparse_sig_raw)."""
+        qhashes, qnhash, rhashes, rnhash = rect_arrays(qhashes, qnhash, rhashes, rnhash, self.s)
+        Q, N = len(qnhash), len(rnhash)
+        ql, rl = _lengths(qlength, Q), _lengths(rlength, N)
+        q0, q1 = self._rect_range(Q, q0, q1)
+        cap = 0 if pairs is None else len(pairs)
+        cm = None if cmin is None else np.ascontiguousarray(cmin, dtype=np.uint32)
+        n, listed = C.c_uint64(0), C.c_uint64(0)
+        rc = lib().drephip_dist_rect_sparse_sig(self._h, qhashes.reshape(-1), qnhash, Q, rhashes.reshape(-1), rnhash, N,
+                                                q0, q1, ql, rl, float(max_p), _ptr(cm),
+                                                pairs.ctypes.data if cap else None, cap, _ptr(pval), C.byref(n),
+                                                C.byref(listed))
+        if rc != self.ERR_NOMEM:
+            check(rc, "drephip_dist_rect_sparse_sig")
+        return rc, n.value, listed.value
+
+    def dist_rect_sparse_sig(self, qhashes, qnhash, rhashes, rnhash, qlength, rlength, max_p: float = 1.0,
+                             cmin: Optional[np.ndarray] = None, q0: int = 0, q1: Optional[int] = None,
+                             cap: Optional[int] = None):
+        """dist_rect_sparse with Mash's p-value per record and the -v / -d
+        filters applied on the GPU before the copy
+        (drephip_dist_rect_sparse_sig): (q, r, common, denom, p, n_listed), the
+        records sorted by (q, r)."""
+        qhashes, qnhash, rhashes, rnhash = rect_arrays(qhashes, qnhash, rhashes, rnhash, self.s)
+        Q, N = len(qnhash), len(rnhash)
+        ql, rl = _lengths(qlength, Q), _lengths(rlength, N)
+        a, b = self._rect_range(Q, q0, q1)
+
+        def call(qlen, rlen, *rest):
+            return lib().drephip_dist_rect_sparse_sig(self._h, qhashes.reshape(-1), qnhash, Q, rhashes.reshape(-1),
+                                                      rnhash, N, a, b, qlen, rlen, *rest)
+        rec, pv, listed = self._sig_call(call, "drephip_dist_rect_sparse_sig", Q, (ql, rl), max_p, cmin, cap, True)
+        return _sorted_sig(rec, pv) + (listed,)
 
     def sparse_stats(self) -> dict:
         """{blocks, direct, fallback, scratch_bytes} of the last sparse all-pairs call."""

@@ -135,7 +135,7 @@ int drephip::refuse_if_pending(drephip_ctx *ctx) {
     return DREPHIP_ERR_ARG;
 }
 
-DREPHIP_EXPORT int drephip_version(void) { return 400; }
+DREPHIP_EXPORT int drephip_version(void) { return 500; }
 
 #ifndef DREPHIP_SRC_DIGEST
 #define DREPHIP_SRC_DIGEST "unknown"
@@ -960,6 +960,135 @@ DREPHIP_EXPORT int drephip_dist_rect_sparse(drephip_ctx *ctx, const uint64_t *qh
     if (have) HIPC(hipMemcpyAsync(pairs, d_p, have * 16, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     return rc;
+}
+
+// ------------------------------------------------------------ significance
+// The record calls with Mash's p-value and its -v / -d filters applied on the
+// device, before the copy (pvalue.hip).
+static int sig_args(drephip_ctx *ctx, double max_p, bool null_arg) {
+    if (null_arg) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    if (!(max_p >= 0.0 && max_p <= 1.0)) { set_error("max_p must lie in [0, 1]"); return DREPHIP_ERR_ARG; }
+    (void)ctx;
+    return DREPHIP_OK;
+}
+
+// a genome that holds a hash has a length (of at least k)
+static int check_lengths(const uint64_t *length, const uint32_t *nhash, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++)
+        if (nhash[i] && !length[i]) { set_error("a genome with a non-empty sketch has length 0"); return DREPHIP_ERR_ARG; }
+    return DREPHIP_OK;
+}
+
+// What the two _sig forms share once the `listed` records are in d_rec: the
+// lengths and cmin staged, the p-values, the stable filter, and the survivors
+// (at most cap) copied out with their p-values.
+static int sig_finish(drephip_ctx *ctx, const uint4 *d_rec, uint64_t listed, const uint64_t *len_a, uint32_t n_a,
+                      const uint64_t *len_b, uint32_t n_b, double max_p, const uint32_t *cmin, uint32_t *pairs,
+                      uint64_t cap, double *pval, uint64_t *n_pairs, hipStream_t st) {
+    *n_pairs = 0;
+    if (listed == 0) return DREPHIP_OK;
+    uint64_t *d_la, *d_lb;
+    uint32_t *d_cmin = nullptr;
+    double *d_p, *d_pout;
+    uint4 *d_out;
+    int rc;
+    if ((rc = scratch(ctx, "sig_len_a", n_a * 8ull, (void **)&d_la))) return rc;
+    HIPC(hipMemcpyAsync(d_la, len_a, n_a * 8ull, hipMemcpyHostToDevice, st));
+    d_lb = d_la;
+    if (len_b != len_a || n_b != n_a) {
+        if ((rc = scratch(ctx, "sig_len_b", n_b * 8ull, (void **)&d_lb))) return rc;
+        HIPC(hipMemcpyAsync(d_lb, len_b, n_b * 8ull, hipMemcpyHostToDevice, st));
+    }
+    if (cmin) {
+        if ((rc = scratch(ctx, "sig_cmin", (ctx->s + 1) * 4ull, (void **)&d_cmin))) return rc;
+        HIPC(hipMemcpyAsync(d_cmin, cmin, (ctx->s + 1) * 4ull, hipMemcpyHostToDevice, st));
+    }
+    if ((rc = scratch(ctx, "sig_p", listed * 8, (void **)&d_p))) return rc;
+    if ((rc = scratch(ctx, "sig_out", listed * 16, (void **)&d_out))) return rc;
+    if ((rc = scratch(ctx, "sig_pout", listed * 8, (void **)&d_pout))) return rc;
+    if ((rc = pvalue_records_impl(ctx, d_rec, listed, d_la, n_a, d_lb, n_b, d_p, st))) return rc;
+    uint64_t kept = 0;
+    if ((rc = records_filter_impl(ctx, d_rec, d_p, listed, max_p, d_cmin, d_out, d_pout, &kept, st))) return rc;
+    *n_pairs = kept;
+    const uint64_t have = std::min(kept, cap);
+    if (have) {
+        HIPC(hipMemcpyAsync(pairs, d_out, have * 16, hipMemcpyDeviceToHost, st));
+        if (pval) HIPC(hipMemcpyAsync(pval, d_pout, have * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIPC(hipStreamSynchronize(st));
+    if (kept > cap) { set_error("more records than cap"); return DREPHIP_ERR_NOMEM; }
+    return DREPHIP_OK;
+}
+
+DREPHIP_EXPORT int drephip_allpairs_sparse_sig(drephip_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash,
+                                               uint32_t N, uint32_t row0, uint32_t row1, const uint64_t *length,
+                                               double max_p, const uint32_t *cmin, uint32_t *pairs, uint64_t cap,
+                                               double *pval, uint64_t *n_pairs, uint64_t *n_listed) {
+    GUARD_CTX(ctx);
+    int rc;
+    if ((rc = sig_args(ctx, max_p, !hashes || !nhash || !length || !n_pairs || (cap && !pairs)))) return rc;
+    *n_pairs = 0;
+    if (n_listed) *n_listed = 0;
+    const uint32_t s = ctx->s;
+    if ((rc = check_rows(hashes, nhash, N, s)) || (rc = check_lengths(length, nhash, N))) return rc;
+    if (row1 > N) row1 = N;
+    if (N < 2 || row0 >= row1 || row0 >= N - 1) return DREPHIP_OK;
+    hipStream_t st = ctx->stream;
+    uint64_t *d_h;
+    uint32_t *d_n;
+    uint4 *d_rec = nullptr;
+    if ((rc = scratch(ctx, "ap_in_h", (uint64_t)N * s * 8, (void **)&d_h))) return rc;
+    if ((rc = scratch(ctx, "ap_in_n", N * 4ull, (void **)&d_n))) return rc;
+    HIPC(hipMemcpyAsync(d_h, hashes, (uint64_t)N * s * 8, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_n, nhash, N * 4ull, hipMemcpyHostToDevice, st));
+    // count first, then room for exactly that many
+    uint64_t listed = 0, again = 0;
+    timing_begin(ctx);
+    rc = allpairs_sparse_impl(ctx, d_h, d_n, N, row0, row1, nullptr, 0, &listed, st);
+    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
+    if (listed) {
+        if ((rc = scratch(ctx, "sig_rec", listed * 16, (void **)&d_rec))) return rc;
+        timing_begin(ctx);
+        if ((rc = allpairs_sparse_impl(ctx, d_h, d_n, N, row0, row1, d_rec, listed, &again, st))) return rc;
+        if (again != listed) { set_error("the record count changed between two runs"); return DREPHIP_ERR_INTERNAL; }
+    }
+    timing_collect(ctx);
+    if (n_listed) *n_listed = listed;
+    return sig_finish(ctx, d_rec, listed, length, N, length, N, max_p, cmin, pairs, cap, pval, n_pairs, st);
+}
+
+DREPHIP_EXPORT int drephip_dist_rect_sparse_sig(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash,
+                                                uint32_t Q, const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N,
+                                                uint32_t q0, uint32_t q1, const uint64_t *qlength,
+                                                const uint64_t *rlength, double max_p, const uint32_t *cmin,
+                                                uint32_t *pairs, uint64_t cap, double *pval, uint64_t *n_pairs,
+                                                uint64_t *n_listed) {
+    GUARD_CTX(ctx);
+    const RectSets in{qhashes, qnhash, Q, rhashes, rnhash, N};
+    int rc;
+    if ((rc = sig_args(ctx, max_p, rect_null(in) || (Q && !qlength) || (N && !rlength) || !n_pairs || (cap && !pairs))))
+        return rc;
+    *n_pairs = 0;
+    if (n_listed) *n_listed = 0;
+    RectSets dev;
+    bool empty;
+    if ((rc = rect_host_stage(ctx, in, q0, &q1, false, &dev, &empty)) || empty) return rc;
+    if ((rc = check_lengths(qlength, qnhash, Q)) || (rc = check_lengths(rlength, rnhash, N))) return rc;
+    hipStream_t st = ctx->stream;
+    uint4 *d_rec = nullptr;
+    uint64_t listed = 0, again = 0;
+    timing_begin(ctx);
+    rc = rect_sparse_impl(ctx, dev, q0, q1, nullptr, 0, &listed, st);
+    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
+    if (listed) {
+        if ((rc = scratch(ctx, "sig_rec", listed * 16, (void **)&d_rec))) return rc;
+        timing_begin(ctx);
+        if ((rc = rect_sparse_impl(ctx, dev, q0, q1, d_rec, listed, &again, st))) return rc;
+        if (again != listed) { set_error("the record count changed between two runs"); return DREPHIP_ERR_INTERNAL; }
+    }
+    timing_collect(ctx);
+    if (n_listed) *n_listed = listed;
+    return sig_finish(ctx, d_rec, listed, qlength, Q, rlength, N, max_p, cmin, pairs, cap, pval, n_pairs, st);
 }
 
 static int rect_top_args(uint32_t top) {

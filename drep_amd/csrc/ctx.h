@@ -407,6 +407,18 @@ int rect_sparse_impl(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t
 int rect_top_impl(drephip_ctx *ctx, const RectSets &in, uint32_t q0, uint32_t q1, uint32_t top, uint32_t *d_hits,
                   uint32_t *d_count, hipStream_t st);
 
+// Significance (pvalue.hip): Mash's p-value per record {a, b, common, denom}
+// (a into d_len_a, b into d_len_b) and per best-hit slot {r, common, denom, 0}
+// (slots at or past the row's count: 1.0), queued on st without a wait; and the
+// stable filter p <= max_p, common >= cmin[denom] (d_pval / d_cmin null: no such
+// test), which waits for its counts.
+int pvalue_records_impl(drephip_ctx *ctx, const uint4 *d_rec, uint64_t n, const uint64_t *d_len_a, uint32_t n_a,
+                        const uint64_t *d_len_b, uint32_t n_b, double *d_pval, hipStream_t st);
+int pvalue_hits_impl(drephip_ctx *ctx, const uint32_t *d_hits, const uint32_t *d_count, uint32_t rows, uint32_t top,
+                     const uint64_t *d_qlen, const uint64_t *d_rlen, uint32_t N, double *d_pval, hipStream_t st);
+int records_filter_impl(drephip_ctx *ctx, const uint4 *d_rec, const double *d_pval, uint64_t n, double max_p,
+                        const uint32_t *d_cmin, uint4 *d_out, double *d_pval_out, uint64_t *n_out, hipStream_t st);
+
 // Primary clustering (linkage.hip).
 int linkage_device_impl(drephip_ctx *ctx, double *d_D, uint32_t n, int method, double *Z_out, hipStream_t st);
 int dist_matrix_impl(drephip_ctx *ctx, const uint16_t *d_common, const uint16_t *d_denom, uint32_t n,

@@ -25,11 +25,21 @@ static inline uint64_t cidx(uint64_t i, uint64_t j, uint64_t N) {      // i < j
     return i * N - i * (i + 1) / 2 + (j - i - 1);
 }
 
+// One line of the table: "reference\tquery\t%g dist\t%g p-value\tcommon/denom".
+static inline void format_line(std::string &out, const char *rname, const std::string &qn, double d, double p, unsigned c,
+                               unsigned dn) {
+    char buf[96];
+    out += rname;
+    out += '\t';
+    out += qn;
+    const int n = snprintf(buf, sizeof(buf), "\t%g\t%g\t%u/%u\n", d, p, c, dn);
+    out.append(buf, (size_t)n);
+}
+
 // Row q of the table (every reference r against query q) appended to out.
 static void format_row(std::string &out, uint32_t q, uint32_t N, const char *const *names,
                        const uint16_t *common, const uint16_t *denom, uint16_t s_denom, const double *dist,
                        const double *pval, const uint16_t *self_count, const double *self_pval) {
-    char buf[96];
     const std::string qn = names[q];
     for (uint32_t r = 0; r < N; r++) {
         double d, p;
@@ -45,26 +55,24 @@ static void format_row(std::string &out, uint32_t q, uint32_t N, const char *con
             c = common[t];
             dn = denom ? denom[t] : s_denom;
         }
-        out += names[r];
-        out += '\t';
-        out += qn;
-        const int n = snprintf(buf, sizeof(buf), "\t%g\t%g\t%u/%u\n", d, p, c, dn);
-        out.append(buf, (size_t)n);
+        format_line(out, names[r], qn, d, p, c, dn);
     }
 }
 
-}  // namespace drephip
+// Row q of the rectangle's table: every reference against query q, the cells
+// as computed (no diagonal rule).
+static void format_rect_row(std::string &out, uint32_t q, uint32_t N, const char *const *rnames, const char *qname,
+                            const uint16_t *common, const uint16_t *denom, uint16_t s_denom, const double *dist,
+                            const double *pval) {
+    const std::string qn = qname;
+    const uint64_t o = (uint64_t)q * N;
+    for (uint32_t r = 0; r < N; r++)
+        format_line(out, rnames[r], qn, dist[o + r], pval[o + r], common[o + r], denom ? denom[o + r] : s_denom);
+}
 
-using namespace drephip;
-
-DREPHIP_EXPORT int drephip_write_mash_table(const char *path, const char *const *names, uint32_t N,
-                                            const uint16_t *common, const uint16_t *denom, uint32_t s,
-                                            const double *dist, const double *pval, const uint16_t *self_count,
-                                            const double *self_pval, int threads) {
-    if (!path || (N && (!names || !self_count || !self_pval))) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    if (N > 1 && (!common || !dist || !pval)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    for (uint32_t i = 0; i < N; i++)
-        if (!names[i]) { set_error("null genome name"); return DREPHIP_ERR_ARG; }
+// nrows rows formatted by `format(row, out)` on T threads in blocks, written in order
+template <class F>
+static int write_rows(const char *path, uint32_t nrows, int threads, F format) {
     FILE *fh = fopen(path, "wb");
     if (!fh) { set_error(std::string("cannot open ") + path); return DREPHIP_ERR_IO; }
     unsigned T = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
@@ -73,13 +81,13 @@ DREPHIP_EXPORT int drephip_write_mash_table(const char *path, const char *const 
     const uint32_t block = std::max<uint32_t>(T, 4 * T);
     std::vector<std::string> rows(block);
     int rc = DREPHIP_OK;
-    for (uint32_t q0 = 0; q0 < N && rc == DREPHIP_OK; q0 += block) {
-        const uint32_t nb = std::min(block, N - q0);
+    for (uint32_t q0 = 0; q0 < nrows && rc == DREPHIP_OK; q0 += block) {
+        const uint32_t nb = std::min(block, nrows - q0);
         const unsigned Tb = std::min<unsigned>(T, nb);
         auto work = [&](unsigned t) {
             for (uint32_t i = t; i < nb; i += Tb) {
                 rows[i].clear();
-                format_row(rows[i], q0 + i, N, names, common, denom, (uint16_t)s, dist, pval, self_count, self_pval);
+                format(q0 + i, rows[i]);
             }
         };
         std::vector<std::thread> pool;
@@ -95,4 +103,36 @@ DREPHIP_EXPORT int drephip_write_mash_table(const char *path, const char *const 
     }
     if (fclose(fh) != 0 && rc == DREPHIP_OK) { set_error(std::string("close failed: ") + path); rc = DREPHIP_ERR_IO; }
     return rc;
+}
+
+}  // namespace drephip
+
+using namespace drephip;
+
+DREPHIP_EXPORT int drephip_write_mash_table(const char *path, const char *const *names, uint32_t N,
+                                            const uint16_t *common, const uint16_t *denom, uint32_t s,
+                                            const double *dist, const double *pval, const uint16_t *self_count,
+                                            const double *self_pval, int threads) {
+    if (!path || (N && (!names || !self_count || !self_pval))) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    if (N > 1 && (!common || !dist || !pval)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    for (uint32_t i = 0; i < N; i++)
+        if (!names[i]) { set_error("null genome name"); return DREPHIP_ERR_ARG; }
+    return write_rows(path, N, threads, [&](uint32_t q, std::string &out) {
+        format_row(out, q, N, names, common, denom, (uint16_t)s, dist, pval, self_count, self_pval);
+    });
+}
+
+DREPHIP_EXPORT int drephip_write_mash_table_rect(const char *path, const char *const *rnames, uint32_t N,
+                                                 const char *const *qnames, uint32_t Q, const uint16_t *common,
+                                                 const uint16_t *denom, uint32_t s, const double *dist,
+                                                 const double *pval, int threads) {
+    if (!path || (N && !rnames) || (Q && !qnames)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    if (N && Q && (!common || !dist || !pval)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
+    for (uint32_t i = 0; i < N; i++)
+        if (!rnames[i]) { set_error("null genome name"); return DREPHIP_ERR_ARG; }
+    for (uint32_t i = 0; i < Q; i++)
+        if (!qnames[i]) { set_error("null genome name"); return DREPHIP_ERR_ARG; }
+    return write_rows(path, Q, threads, [&](uint32_t q, std::string &out) {
+        format_rect_row(out, q, N, rnames, qnames[q], common, denom, (uint16_t)s, dist, pval);
+    });
 }

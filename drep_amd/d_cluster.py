@@ -458,18 +458,74 @@ def mash_pvalue(common: np.ndarray, len_r: np.ndarray, len_q: np.ndarray, s: int
     return np.where(c == 0, 1.0, p)
 
 
-def write_mash_table(path: str, cm: CondensedMash, threads: int = 0) -> None:
+def mash_pvalue_device(common: np.ndarray, len_a: np.ndarray, len_b: np.ndarray, s: int, gpu: int = 0) -> np.ndarray:
+    """mash_pvalue on the GPU (libdrephip drephip_pvalue_records, kernel
+    k_pvalue_records): Mash's own arithmetic restated with IEEE operations
+    only, bit for bit _lib.pvalue_eval; against mash_pvalue (scipy) the values
+    agree to about 1e-12 relative, and values below 2^-1022 are 0.0."""
+    common = np.ascontiguousarray(common, dtype=np.uint32).reshape(-1)
+    n = len(common)
+    if n == 0:
+        return np.zeros(0, dtype=np.float64)
+    if int(common.max()) > s:
+        raise ValueError("common must not exceed s")
+    rec = np.empty((n, 4), dtype=np.uint32)
+    rec[:, 0] = rec[:, 1] = np.arange(n, dtype=np.uint32)
+    rec[:, 2] = common
+    rec[:, 3] = s
+    la = np.broadcast_to(np.asarray(len_a, dtype=np.uint64).reshape(-1), (n,))
+    lb = np.broadcast_to(np.asarray(len_b, dtype=np.uint64).reshape(-1), (n,))
+    with _lib.Context(device=gpu, k=MASH_K, s=s, seed=MASH_SEED) as ctx:
+        return ctx.pvalue_records(rec, la, lb)
+
+
+_CMIN_CACHE = {}
+
+
+def min_common_table(max_dist: float, s: int, k: int = MASH_K) -> np.ndarray:
+    """Mash's -d <max_dist> as a rule on counts: uint32 [s + 1], entry d the
+    smallest common with float64 Mash distance (drephip_distance_lut at
+    denominator d) <= max_dist, or d + 1 when no count reaches it.  A pair
+    passes when common >= table[denom]: the comparison mdb_from_rect makes,
+    bit for bit, since the distance falls as common grows.  Entry 0 (two empty
+    sketches, distance 0) is 0."""
+    key = (float(max_dist), int(s), int(k))
+    if key not in _CMIN_CACHE:
+        out = np.empty(s + 1, dtype=np.uint32)
+        out[0] = 0 if 0.0 <= key[0] else 1
+        for d in range(1, s + 1):
+            ok = np.nonzero(_lib.distance_lut(d, k) <= key[0])[0]
+            out[d] = ok[0] if len(ok) else d + 1
+        _CMIN_CACHE[key] = out
+    return _CMIN_CACHE[key].copy()
+
+
+def _pvalue_by(how: str, common, len_a, len_b, s: int, gpu: int = 0) -> np.ndarray:
+    """The p-values by 'host' (scipy, mash_pvalue), 'device' (the GPU kernel)
+    or 'eval' (the kernel's arithmetic on the host, no GPU)."""
+    if how == 'host':
+        return mash_pvalue(common, len_a, len_b, s)
+    if how == 'device':
+        return mash_pvalue_device(common, len_a, len_b, s, gpu)
+    if how == 'eval':
+        return _lib.pvalue_eval(common, len_a, len_b, s, MASH_K)
+    raise ValueError("pvalue must be 'host', 'device' or 'eval', got %r" % (how,))
+
+
+def write_mash_table(path: str, cm: CondensedMash, threads: int = 0, pvalue: str = 'host', gpu: int = 0) -> None:
     """MASH_table.tsv as `mash dist ALL ALL` prints it (d_cluster.py:570-572):
     reference, query, %g distance, %g p-value, common/denom; outer loop over
     queries.  N^2 lines (10^8 at 10^4 genomes).  Distances (per-denominator
     tables) and p-values are computed once per unordered pair -- both are
     symmetric in (reference, query) -- and only for pairs sharing a hash (the
     p-value of c = 0 is 1); libdrephip formats the text on `threads` host
-    threads (drephip_write_mash_table)."""
+    threads (drephip_write_mash_table).  pvalue: 'host' (scipy, the
+    default), 'device' (the p-values on GPU `gpu`, mash_pvalue_device) or
+    'eval' (the same arithmetic on the host)."""
     N = len(cm.names)
     common = np.asarray(cm.common, dtype=np.uint16)
     denom = np.asarray(cm.denom, dtype=np.uint16)
-    length = np.asarray(cm.length, dtype=np.float64)
+    length = np.asarray(cm.length, dtype=np.float64 if pvalue == 'host' else np.uint64)
     dist = np.empty(len(common), dtype=np.float64)
     for d in np.unique(denom):
         sel = denom == d
@@ -479,9 +535,9 @@ def write_mash_table(path: str, cm: CondensedMash, threads: int = 0) -> None:
     nz = np.nonzero(common)[0]
     if len(nz):
         iu, ju = _condensed_ij(nz, N)
-        pval[nz] = mash_pvalue(common[nz], length[iu], length[ju], cm.s)
+        pval[nz] = _pvalue_by(pvalue, common[nz], length[iu], length[ju], cm.s, gpu)
     self_count = np.minimum(np.asarray(cm.nhash, dtype=np.int64), cm.s).astype(np.uint16)
-    self_pval = mash_pvalue(self_count, length, length, cm.s)
+    self_pval = _pvalue_by(pvalue, self_count, length, length, cm.s, gpu)
     full = bool((denom == cm.s).all())
     _lib.write_mash_table(path, list(cm.locations), common, None if full else denom, cm.s, dist, pval,
                           self_count, self_pval, threads)
@@ -727,6 +783,7 @@ class SparseMash:
     nhash: np.ndarray
     length: np.ndarray
     s: int
+    pval: Optional[np.ndarray] = None   # float64 per listed pair (all_vs_all_MASH_sparse with max_p / max_dist)
 
 
 def sparse_allpairs(hashes: np.ndarray, nhash: np.ndarray, s: int, devices: Sequence[int] = (0,)):
@@ -750,15 +807,58 @@ def sparse_allpairs(hashes: np.ndarray, nhash: np.ndarray, s: int, devices: Sequ
     return tuple(np.concatenate([r[k] for r in res]) for k in range(4))
 
 
-def all_vs_all_MASH_sparse(Bdb, data_folder, **kwargs) -> SparseMash:
+def _check_sig(max_p, max_dist):
+    if max_p is not None and not (0 <= float(max_p) <= 1):
+        raise ValueError("max_p must be in [0, 1]")
+    if max_dist is not None and not (0 <= float(max_dist) < 1):
+        raise ValueError("max_dist must be in [0, 1): the record form lists only pairs that share a hash")
+
+
+def sparse_allpairs_sig(hashes: np.ndarray, nhash: np.ndarray, length: np.ndarray, s: int,
+                        max_p: Optional[float] = None, max_dist: Optional[float] = None,
+                        devices: Sequence[int] = (0,)):
+    """sparse_allpairs with Mash's p-value per pair and its -v <max_p> /
+    -d <max_dist> filters applied on the GPU, before the list comes to the host
+    (libdrephip drephip_allpairs_sparse_sig): (i, j, common, denom, p), sorted
+    by (i, j).  Rows split over the devices as sparse_allpairs splits them."""
+    _check_sig(max_p, max_dist)
+    N = len(nhash)
+    parts = row_partition(N, len(devices))
+    cmin = None if max_dist is None else min_common_table(max_dist, s)
+    mp = 1.0 if max_p is None else float(max_p)
+    none = tuple(np.zeros(0, t) for t in (np.uint32, np.uint32, np.uint16, np.uint16, np.float64))
+
+    def run(k, dev):
+        r0, r1 = parts[k]
+        if r1 <= r0:
+            return none
+        with _lib.Context(device=dev, k=MASH_K, s=s, seed=MASH_SEED) as ctx:
+            return ctx.allpairs_sparse_sig(hashes, nhash, length, mp, cmin, r0, r1)[:5]
+    res = _on_devices(list(devices), run) if N >= 2 else []
+    if not res:
+        return none
+    return tuple(np.concatenate([r[k] for r in res]) for k in range(5))
+
+
+def all_vs_all_MASH_sparse(Bdb, data_folder, max_p=None, max_dist=None, **kwargs) -> SparseMash:
     """Sketch (or load cached sketches) and run the sparse HIP all-pairs: the
     pairs that share a hash instead of the condensed triangle (reference
     drep/d_cluster.py:481-596 keeps every pair as a row of MASH_table.tsv).
-    Same keyword arguments as all_vs_all_MASH_condensed."""
+    Same keyword arguments as all_vs_all_MASH_condensed.
+
+    max_p / max_dist (default None: every pair that shares a hash, as before):
+    Mash's -v and -d.  With either one the p-values are computed on the GPU,
+    only the pairs with p <= max_p and float64 Mash distance <= max_dist are
+    listed, and the result's pval holds their p-values."""
     sk = sketch_genomes(Bdb, data_folder, **kwargs)
+    if max_p is None and max_dist is None:
+        with _Stage('allpairs_s'):
+            i, j, common, denom = sparse_allpairs(sk.hashes, sk.nhash, sk.s, _devices(kwargs))
+        return SparseMash(sk.names, sk.locations, i, j, common, denom, sk.nhash, sk.length, sk.s)
     with _Stage('allpairs_s'):
-        i, j, common, denom = sparse_allpairs(sk.hashes, sk.nhash, sk.s, _devices(kwargs))
-    return SparseMash(sk.names, sk.locations, i, j, common, denom, sk.nhash, sk.length, sk.s)
+        i, j, common, denom, p = sparse_allpairs_sig(sk.hashes, sk.nhash, sk.length, sk.s, max_p, max_dist,
+                                                     _devices(kwargs))
+    return SparseMash(sk.names, sk.locations, i, j, common, denom, sk.nhash, sk.length, sk.s, p)
 
 
 def _sparse_pairs(sm: SparseMash):
@@ -854,6 +954,7 @@ class RectMash:
     qlength: np.ndarray
     rlength: np.ndarray
     s: int
+    pval: Optional[np.ndarray] = None  # record form with pvalue / max_p: float64 per record
 
 
 def _query_ranges(Q: int, n: int) -> List[tuple]:
@@ -910,6 +1011,33 @@ def rect_allpairs_sparse(qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.nd
     return tuple(np.concatenate([x[k] for x in res]) for k in range(4))
 
 
+def rect_allpairs_sparse_sig(qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray,
+                             qlength: np.ndarray, rlength: np.ndarray, s: int, max_p: Optional[float] = None,
+                             max_dist: Optional[float] = None, devices: Sequence[int] = (0,)):
+    """rect_allpairs_sparse with Mash's p-value per pair and its -v <max_p> /
+    -d <max_dist> filters applied on the GPU, before the list comes to the host
+    (libdrephip drephip_dist_rect_sparse_sig): (q, r, common, denom, p), sorted
+    by (q, r)."""
+    _check_sig(max_p, max_dist)
+    qhashes, qnhash, rhashes, rnhash = _lib.rect_arrays(qhashes, qnhash, rhashes, rnhash, s)
+    Q, N = len(qnhash), len(rnhash)
+    none = tuple(np.zeros(0, t) for t in (np.uint32, np.uint32, np.uint16, np.uint16, np.float64))
+    parts = _query_ranges(Q, len(devices))
+    cmin = None if max_dist is None else min_common_table(max_dist, s)
+    mp = 1.0 if max_p is None else float(max_p)
+
+    def run(k, dev):
+        a, b = parts[k]
+        if b <= a:
+            return none
+        with _lib.Context(device=dev, k=MASH_K, s=s, seed=MASH_SEED) as ctx:
+            return ctx.dist_rect_sparse_sig(qhashes, qnhash, rhashes, rnhash, qlength, rlength, mp, cmin, a, b)[:5]
+    if not (Q and N):
+        return none
+    res = _on_devices(list(devices), run)
+    return tuple(np.concatenate([x[k] for x in res]) for k in range(5))
+
+
 _MAX_SKETCH = 32767      # drephip_max_sketch(): counts and denominators are uint16
 
 
@@ -964,7 +1092,9 @@ def _query_inputs(Qdb, data_folder, reference, max_dist, kwargs):
         reference = os.path.join(data_folder, 'MASH_files', 'ALL.msh')
     ref = _read_reference(reference, kwargs)
     qfolder = kwargs.get('query_folder', os.path.join(data_folder, 'MASH_query'))
-    skw = {k: v for k, v in kwargs.items() if k not in ('query_folder', 'max_dist')}
+    _check_sig(kwargs.get('max_p', None), None)
+    skw = {k: v for k, v in kwargs.items()
+           if k not in ('query_folder', 'max_dist', 'max_p', 'pvalue', 'write_table')}
     skw['MASH_sketch'] = ref[5]
     sk = sketch_genomes(Qdb, qfolder, **skw)
     return ref, sk, _devices(kwargs)
@@ -982,22 +1112,69 @@ def query_vs_MASH_rect(Qdb, data_folder, reference=None, **kwargs) -> RectMash:
     cache) by sketch_genomes into kwargs['query_folder'] (default
     <data_folder>/MASH_query), so <data_folder>/MASH_files is never modified.
     max_dist (default None: the dense Q x N form): the record form, only the
-    pairs that share a hash.  gpu, gpus, processors and ingest as in
-    all_vs_all_MASH."""
-    max_dist = kwargs.get('max_dist', None)
+    pairs that share a hash.  max_p (default None), Mash's -v: selects the
+    record form as max_dist does; pvalue=True with either: the records carry
+    their p-values (the result's pval).  With max_p or pvalue the record form
+    runs drephip_dist_rect_sparse_sig: the p-values are computed on the GPU and
+    the records above max_p, or beyond max_dist, are dropped there, before the
+    list comes to the host.  write_table=<path> (dense form only): the text of
+    `mash dist <reference.msh> <query.msh>` written by write_mash_table_rect.
+    gpu, gpus, processors and ingest as in all_vs_all_MASH."""
+    max_dist, max_p = kwargs.get('max_dist', None), kwargs.get('max_p', None)
+    want_p = bool(kwargs.get('pvalue', False)) or max_p is not None
+    table = kwargs.get('write_table', None)
+    record_form = max_dist is not None or max_p is not None
+    if table is not None and record_form:
+        raise ValueError("write_table needs the dense form: no max_dist, no max_p")
     (rnames, rlocs, rh, rn, rlen, s), sk, devs = _query_inputs(Qdb, data_folder, reference, max_dist, kwargs)
+    pval = None
     with _Stage('rect_s'):
-        if max_dist is None:
+        if not record_form:
             common, denom = rect_allpairs(sk.hashes, sk.nhash, rh, rn, s, devs)
             rec = (None, None, None, None)
+        elif want_p:
+            common = denom = None
+            rec = rect_allpairs_sparse_sig(sk.hashes, sk.nhash, rh, rn, sk.length, rlen, s, max_p, max_dist, devs)
+            pval = rec[4]
         else:
             common = denom = None
             rec = rect_allpairs_sparse(sk.hashes, sk.nhash, rh, rn, s, devs)
-    return RectMash(sk.names, sk.locations, rnames, rlocs, common, denom, rec[0], rec[1], rec[2], rec[3],
-                    sk.nhash, rn, sk.length, rlen, s)
+    rm = RectMash(sk.names, sk.locations, rnames, rlocs, common, denom, rec[0], rec[1], rec[2], rec[3],
+                  sk.nhash, rn, sk.length, rlen, s, pval)
+    if table is not None:
+        with _Stage('table_s'):
+            write_mash_table_rect(table, rm, kwargs.get('processors', 0) or 0, gpu=devs[0])
+    return rm
 
 
-def mdb_from_rect(rm: RectMash, k: int = MASH_K, max_dist: Optional[float] = None) -> pd.DataFrame:
+def write_mash_table_rect(path: str, rm: RectMash, threads: int = 0, pvalue: str = 'device', gpu: int = 0) -> None:
+    """The text `mash dist <reference.msh> <query.msh>` prints (the two-file
+    form of drep/d_cluster.py:569-573) from the dense rectangle: Q x N lines,
+    query outer, reference inner: reference, query, %g distance, %g p-value,
+    common/denom, the names as the sketch files hold them.  No diagonal rule: a
+    query that is also a reference prints its cell as computed.  The p-values
+    are computed for the cells that share a hash (1 elsewhere) by `pvalue`:
+    'device' (GPU `gpu`, the default), 'eval' (the same arithmetic on the host)
+    or 'host' (scipy); libdrephip formats the text on `threads` host threads
+    (drephip_write_mash_table_rect)."""
+    if rm.common is None:
+        raise ValueError("write_mash_table_rect needs the dense form of the rectangle")
+    Q, N = len(rm.qnames), len(rm.rnames)
+    common = np.ascontiguousarray(rm.common, dtype=np.uint16).reshape(Q, N)
+    denom = np.ascontiguousarray(rm.denom, dtype=np.uint16).reshape(Q, N)
+    dist = _rect_distance64(common, denom)
+    pval = np.ones((Q, N), dtype=np.float64)
+    q, r = np.nonzero(common)
+    if len(q):
+        pval[q, r] = _pvalue_by(pvalue, common[q, r], np.asarray(rm.qlength, dtype=np.uint64)[q],
+                                np.asarray(rm.rlength, dtype=np.uint64)[r], rm.s, gpu)
+    full = bool((denom == rm.s).all())
+    _lib.write_mash_table_rect(path, list(rm.rlocations), list(rm.qlocations), common, None if full else denom, rm.s,
+                               dist, pval, threads)
+
+
+def mdb_from_rect(rm: RectMash, k: int = MASH_K, max_dist: Optional[float] = None, max_p: Optional[float] = None,
+                  pvalue: bool = False) -> pd.DataFrame:
     """The table dRep's parse (drep/d_cluster.py:575-585) makes of `mash dist
     <reference> <queries>`: rows query-outer, reference-inner; genome1 the
     reference name, genome2 the query name, each an ordered categorical over
@@ -1005,8 +1182,15 @@ def mdb_from_rect(rm: RectMash, k: int = MASH_K, max_dist: Optional[float] = Non
     (float32_tables), similarity = 1 - dist.  The record form gives the rows of
     the listed pairs (plus empty query against empty reference, distance 0 to
     Mash), in the same order; max_dist keeps the rows whose float64 Mash
-    distance (drephip_distance_lut) is <= max_dist."""
+    distance (drephip_distance_lut) is <= max_dist.  max_p keeps the rows with
+    p <= max_p and pvalue=True adds the float64 column p; both need the
+    record form's p-values (rm.pval, from drephip_dist_rect_sparse_sig; a pair
+    of two empty sketches has p = 1)."""
     Q, N = len(rm.qnames), len(rm.rnames)
+    want_p = pvalue or max_p is not None
+    if want_p and (rm.common is not None or rm.pval is None):
+        raise ValueError("p-values need the record form computed with pvalue=True or max_p")
+    p = np.asarray(rm.pval, dtype=np.float64) if want_p else None
     if rm.common is not None:
         q = np.repeat(np.arange(Q, dtype=np.int64), N)
         r = np.tile(np.arange(N, dtype=np.int64), Q)
@@ -1023,16 +1207,26 @@ def mdb_from_rect(rm: RectMash, k: int = MASH_K, max_dist: Optional[float] = Non
             c = np.concatenate([c, np.zeros(len(eq) * len(er), np.uint16)])
             d = np.concatenate([d, np.zeros(len(eq) * len(er), np.uint16)])
             order = np.argsort(q * max(N, 1) + r, kind='stable')
+            if p is not None:
+                p = np.concatenate([p, np.ones(len(eq) * len(er))])[order]
             q, r, c, d = q[order], r[order], c[order], d[order]
-    if max_dist is not None:
-        keep = _rect_distance64(c, d, k) <= float(max_dist)
+    if max_dist is not None or max_p is not None:
+        keep = np.ones(len(c), dtype=bool)
+        if max_dist is not None:
+            keep &= _rect_distance64(c, d, k) <= float(max_dist)
+        if max_p is not None:
+            keep &= p <= float(max_p)
         q, r, c, d = q[keep], r[keep], c[keep], d[keep]
+        p = p[keep] if p is not None else None
     dens = np.unique(d) if len(d) else np.array([rm.s])
     lut32, lut_off = float32_tables(dens, rm.s, k)
     dist = lut32[lut_off[d.astype(np.int64)].astype(np.int64) + c.astype(np.int64)].astype(np.float32) if len(d) \
         else np.zeros(0, np.float32)
-    return pd.DataFrame({'genome1': _name_categorical(rm.rnames, r), 'genome2': _name_categorical(rm.qnames, q),
-                         'dist': dist, 'similarity': np.float32(1) - dist}, copy=False)
+    cols = {'genome1': _name_categorical(rm.rnames, r), 'genome2': _name_categorical(rm.qnames, q),
+            'dist': dist, 'similarity': np.float32(1) - dist}
+    if pvalue:
+        cols['p'] = p
+    return pd.DataFrame(cols, copy=False)
 
 
 def _name_categorical(names, idx):
@@ -1054,15 +1248,19 @@ def query_vs_MASH(Qdb, data_folder, reference=None, **kwargs):
     Q x N rows): only the rows whose float64 Mash distance is <= max_dist,
     from the record form of the kernel.  This is this library's own filter:
     Mash's -d option cannot be pinned here, because no Mash binary is available
-    to compare against.
+    to compare against.  max_p (default None), Mash's -v: only the rows with
+    p-value <= max_p; it selects the record form as max_dist does.  pvalue=True
+    (with max_dist or max_p): a float64 column p.  With either one the p-values
+    and both filters run on the GPU (drephip_dist_rect_sparse_sig).
 
     Returns:
-        DataFrame [genome1 (reference), genome2 (query), dist, similarity],
-        rows query-outer, reference-inner
+        DataFrame [genome1 (reference), genome2 (query), dist, similarity
+        (, p)], rows query-outer, reference-inner
     """
     rm = query_vs_MASH_rect(Qdb, data_folder, reference, **kwargs)
     with _Stage('mdb_s'):
-        return mdb_from_rect(rm, max_dist=kwargs.get('max_dist', None))
+        return mdb_from_rect(rm, max_dist=kwargs.get('max_dist', None), max_p=kwargs.get('max_p', None),
+                             pvalue=bool(kwargs.get('pvalue', False)))
 
 
 def union_condensed(cm_ref: CondensedMash, rm: RectMash, cm_query: CondensedMash) -> CondensedMash:
@@ -1137,9 +1335,12 @@ def rect_top_hits(qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, 
 
 def best_hits_frame(qnames: Sequence[str], rnames: Sequence[str], ref: np.ndarray, common: np.ndarray,
                     denom: np.ndarray, count: np.ndarray, s: int, k: int = MASH_K,
-                    max_dist: Optional[float] = None) -> pd.DataFrame:
+                    max_dist: Optional[float] = None, pval: Optional[np.ndarray] = None,
+                    max_p: Optional[float] = None) -> pd.DataFrame:
     """rect_top_hits' arrays as the table query_best_hits returns (its
-    docstring).  Pure pandas/numpy plus the distance tables."""
+    docstring).  Pure pandas/numpy plus the distance tables.  pval (float64
+    [Q, top]): the hits' p-values, added as column p; max_p drops the listed
+    hits above it (their ranks stay as selected)."""
     ref, count = np.asarray(ref, dtype=np.int64), np.asarray(count, dtype=np.int64)
     top = ref.shape[1] if ref.ndim == 2 else 0
     listed = np.arange(top, dtype=np.int64)[None, :] < count[:, None]
@@ -1147,19 +1348,39 @@ def best_hits_frame(qnames: Sequence[str], rnames: Sequence[str], ref: np.ndarra
     r = ref[q, rank]
     c = np.asarray(common, dtype=np.uint16)[q, rank]
     d = np.asarray(denom, dtype=np.uint16)[q, rank]
-    if max_dist is not None:
-        keep = _rect_distance64(c, d, k) <= float(max_dist)
+    p = None if pval is None else np.asarray(pval, dtype=np.float64)[q, rank]
+    if max_p is not None and p is None:
+        raise ValueError("max_p needs the hits' p-values")
+    if max_dist is not None or max_p is not None:
+        keep = np.ones(len(c), dtype=bool)
+        if max_dist is not None:
+            keep &= _rect_distance64(c, d, k) <= float(max_dist)
+        if max_p is not None:
+            keep &= p <= float(max_p)
         q, rank, r, c, d = q[keep], rank[keep], r[keep], c[keep], d[keep]
+        p = p[keep] if p is not None else None
     dens = np.unique(d) if len(d) else np.array([s])
     lut32, lut_off = float32_tables(dens, s, k)
     dist = lut32[lut_off[d.astype(np.int64)].astype(np.int64) + c.astype(np.int64)].astype(np.float32) if len(d) \
         else np.zeros(0, np.float32)
-    return pd.DataFrame({'genome1': _name_categorical(rnames, r), 'genome2': _name_categorical(qnames, q),
-                         'rank': rank.astype(np.int32), 'dist': dist, 'similarity': np.float32(1) - dist,
-                         'common': c, 'denom': d}, copy=False)
+    cols = {'genome1': _name_categorical(rnames, r), 'genome2': _name_categorical(qnames, q),
+            'rank': rank.astype(np.int32), 'dist': dist, 'similarity': np.float32(1) - dist, 'common': c, 'denom': d}
+    if p is not None:
+        cols['p'] = p
+    return pd.DataFrame(cols, copy=False)
 
 
-def query_best_hits(Qdb, data_folder, reference=None, top=1, max_dist=None, **kwargs) -> pd.DataFrame:
+def rect_top_pvalues(ref: np.ndarray, common: np.ndarray, denom: np.ndarray, count: np.ndarray, qlength: np.ndarray,
+                     rlength: np.ndarray, s: int, gpu: int = 0) -> np.ndarray:
+    """Mash's p-value of every hit rect_top_hits listed, float64 [Q, top], 1.0
+    in the unused slots, computed on GPU `gpu` (libdrephip
+    drephip_pvalue_hits_device)."""
+    with _lib.Context(device=gpu, k=MASH_K, s=s, seed=MASH_SEED) as ctx:
+        return ctx.pvalue_hits(ref, common, denom, count, qlength, rlength)
+
+
+def query_best_hits(Qdb, data_folder, reference=None, top=1, max_dist=None, pvalue=False, max_p=None,
+                    **kwargs) -> pd.DataFrame:
     """Each genome of Qdb against a reference sketch file: its `top` (1..64)
     nearest references, selected on the GPU.
 
@@ -1167,7 +1388,11 @@ def query_best_hits(Qdb, data_folder, reference=None, top=1, max_dist=None, **kw
     gpus, processors, ingest).  Only references that share a hash with the
     query are ever listed (Mash distance < 1).  max_dist keeps the rows whose
     float64 Mash distance (drephip_distance_lut) is <= max_dist, the rule of
-    mdb_from_rect.
+    mdb_from_rect.  pvalue=True adds Mash's p-value of every hit as the float64
+    column p (computed on the GPU); max_p (Mash's -v; implies the column) drops
+    the rows with p > max_p.  Both filters apply to the listed hits: the `top`
+    nearest are selected first, so a dropped hit is not replaced by a farther
+    one, and the ranks stay as selected.
 
     Returns:
         DataFrame [genome1 (reference), genome2 (query), rank (0-based, nearest
@@ -1176,11 +1401,16 @@ def query_best_hits(Qdb, data_folder, reference=None, top=1, max_dist=None, **kw
         the %g / read_csv route (float32_tables), so a row's dist and
         similarity are bit for bit those of the same pair in query_vs_MASH.
     """
-    (rnames, _, rh, rn, _, s), sk, devs = _query_inputs(Qdb, data_folder, reference, max_dist, kwargs)
+    _check_sig(max_p, None)
+    (rnames, _, rh, rn, rlen, s), sk, devs = _query_inputs(Qdb, data_folder, reference, max_dist, kwargs)
     with _Stage('rect_top_s'):
         ref, common, denom, count = rect_top_hits(sk.hashes, sk.nhash, rh, rn, s, top, devs)
+        pval = None
+        if pvalue or max_p is not None:
+            pval = rect_top_pvalues(ref, common, denom, count, sk.length, rlen, s, devs[0])
     with _Stage('mdb_s'):
-        return best_hits_frame(sk.names, rnames, ref, common, denom, count, s, max_dist=max_dist)
+        return best_hits_frame(sk.names, rnames, ref, common, denom, count, s, max_dist=max_dist, pval=pval,
+                               max_p=max_p)
 
 
 def place_queries(hits: pd.DataFrame, Cdb: pd.DataFrame, P_ani: float = 0.9) -> pd.DataFrame:

@@ -631,6 +631,105 @@ int drephip_dist_rect_top(drephip_ctx *ctx, const uint64_t *qhashes, const uint3
                           const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint32_t q0, uint32_t q1,
                           uint32_t top, uint32_t *hits /* (q1 - q0) x top x 4 */, uint32_t *count /* q1 - q0 */);
 
+/* ---------------------------------------------------------------- significance
+ * Replaces: the p-value column (the fourth) and the options -v <max p-value>
+ * and -d <max distance> of `mash dist`, drep/d_cluster.py:569-573, for every
+ * form of the call that lists records or hits.  Mash's definition, with the
+ * context's k and s (not the pair's denominator):
+ *   kspace = 4^k;  px = 1/(1 + kspace/len_a),  py = 1/(1 + kspace/len_b);
+ *   r = px py / (px + py - px py);  M = kspace (px + py) / (1 + r);
+ *   n = floor(min(M, s));
+ *   p = 1 if common == 0, 0 if common > n, else P(X >= common), X ~ Binomial(n, r).
+ * r and n are formed with these IEEE double operations in this order.  The
+ * tail is summed with IEEE + - x / only (drep_amd/csrc/pvalue.h), by the same
+ * inline functions on the host and in the kernels, compiled without FMA
+ * contraction: the host and device forms agree bit for bit.  A value below
+ * 2^-1022 is 0.0 (no subnormals); the relative error of the others is below
+ * 1e-11 (about (n + 3 common) 2^-53).
+ *
+ * drephip_pvalue_eval.  Replaces: the p-value column of `mash dist`
+ * (drep/d_cluster.py:569-573) for n (common, len_a, len_b) triples, on the
+ * host: no context, no GPU.  r_out / n_out (nullable) receive r and n.  A
+ * length of 0 with common > 0 cannot occur (a genome shorter than k has an
+ * empty sketch): DREPHIP_ERR_ARG. */
+int drephip_pvalue_eval(int k, uint32_t s, const uint32_t *common, const uint64_t *len_a, const uint64_t *len_b,
+                        uint64_t n, double *pval, double *r_out /* nullable */, uint32_t *n_out /* nullable */);
+/* drephip_pvalue_records_device.  Replaces: the p-value column of `mash dist`
+ * (drep/d_cluster.py:569-573) for n records {a, b, common, denom} as the
+ * sparse calls list them (kernel k_pvalue_records, one lane per record): a
+ * indexes d_len_a (n_a entries), b indexes d_len_b (n_b entries) -- triangle
+ * records pass one array twice, rectangle records {q, r} the query and the
+ * reference lengths.  Writes exactly n doubles.  n == 0: DREPHIP_OK; null
+ * pointers: DREPHIP_ERR_ARG.  The value of a record that names a genome
+ * outside its array is NaN, that of one with a zero length and common > 0 is
+ * unspecified.  Blocking, on the caller's stream. */
+int drephip_pvalue_records_device(drephip_ctx *ctx, const uint32_t *d_records /* n x 4 */, uint64_t n,
+                                  const uint64_t *d_len_a, uint32_t n_a, const uint64_t *d_len_b, uint32_t n_b,
+                                  double *d_pval, void *stream);
+/* drephip_pvalue_records.  Replaces: the same column, the host form: the
+ * records and lengths are staged and checked first (a < n_a, b < n_b,
+ * common <= denom <= s, a length >= 1 wherever common > 0; DREPHIP_ERR_ARG
+ * otherwise). */
+int drephip_pvalue_records(drephip_ctx *ctx, const uint32_t *records /* n x 4 */, uint64_t n, const uint64_t *len_a,
+                           uint32_t n_a, const uint64_t *len_b, uint32_t n_b, double *pval);
+/* drephip_pvalue_hits_device.  Replaces: the p-value column of `mash dist`
+ * (drep/d_cluster.py:569-573) for the best hits of drephip_dist_rect_top*:
+ * d_hits holds rows x top hits {r, common, denom, 0}, d_count the listed hits
+ * per row, d_qlen the rows' query lengths (from q0 on), d_rlen the N reference
+ * lengths.  d_pval (rows x top) receives the p-value of every listed hit and
+ * 1.0 in the slots at or past the row's count.  Blocking, on the caller's
+ * stream. */
+int drephip_pvalue_hits_device(drephip_ctx *ctx, const uint32_t *d_hits, const uint32_t *d_count, uint32_t rows,
+                               uint32_t top, const uint64_t *d_qlen, const uint64_t *d_rlen, uint32_t N,
+                               double *d_pval /* rows x top */, void *stream);
+/* drephip_records_filter_device.  Replaces: the options -v <max p-value> and
+ * -d <max distance> of `mash dist` (drep/d_cluster.py:569-573) on a record
+ * list: record t is kept when d_pval[t] <= max_p and common >= d_cmin[denom].
+ * d_pval NULL: no p-value test; d_cmin NULL: no distance test.  d_cmin has
+ * s + 1 entries, built by the caller from drephip_distance_lut: cmin[d] = the
+ * smallest c with lut_d[c] <= max distance, d + 1 when there is none -- the
+ * rule is then the float64 comparison itself.  Stable: the survivors keep
+ * their order, in d_out (and their p-values in d_pval_out, nullable);
+ * *n_out = their number.  The outputs hold up to n entries and must not alias
+ * the inputs.  max_p outside [0, 1] or NaN: DREPHIP_ERR_ARG.  Lists of more
+ * than 2^26 records are filtered in pieces (DREPHIP_FILTER_CHUNK sets fewer
+ * records per piece, for tests).  Blocking, on the caller's stream. */
+int drephip_records_filter_device(drephip_ctx *ctx, const uint32_t *d_records, const double *d_pval /* nullable */,
+                                  uint64_t n, double max_p, const uint32_t *d_cmin /* nullable, s + 1 */,
+                                  uint32_t *d_out, double *d_pval_out /* nullable */, uint64_t *n_out, void *stream);
+/* drephip_allpairs_sparse_sig, drephip_dist_rect_sparse_sig.  Replace:
+ * `mash dist -v <max_p> -d <max distance>` (drep/d_cluster.py:569-573) as
+ * records: the host forms drephip_allpairs_sparse / drephip_dist_rect_sparse
+ * with the genomes' lengths, max_p, a host cmin (nullable, as above), a p-value
+ * per record (pval, nullable, cap entries) and *n_listed (nullable), the
+ * records before the filter.  The matrices are staged and checked as in those
+ * calls (and a genome with a non-empty sketch must have a length >= 1), the
+ * device record call lists the pairs into context scratch (a counting run,
+ * then room for exactly that many), the p-values and the filter run there, and
+ * only the survivors are copied out, in the device call's order.  The cap /
+ * n_pairs / DREPHIP_ERR_NOMEM contract is that of the record calls, applied to
+ * the filtered list.  The record calls themselves are unchanged. */
+int drephip_allpairs_sparse_sig(drephip_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash, uint32_t N,
+                                uint32_t row0, uint32_t row1, const uint64_t *length /* N */, double max_p,
+                                const uint32_t *cmin /* nullable, s + 1 */, uint32_t *pairs /* cap x 4 */, uint64_t cap,
+                                double *pval /* nullable, cap */, uint64_t *n_pairs, uint64_t *n_listed /* nullable */);
+int drephip_dist_rect_sparse_sig(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash, uint32_t Q,
+                                 const uint64_t *rhashes, const uint32_t *rnhash, uint32_t N, uint32_t q0, uint32_t q1,
+                                 const uint64_t *qlength /* Q */, const uint64_t *rlength /* N */, double max_p,
+                                 const uint32_t *cmin /* nullable, s + 1 */, uint32_t *pairs /* cap x 4 */, uint64_t cap,
+                                 double *pval /* nullable, cap */, uint64_t *n_pairs, uint64_t *n_listed /* nullable */);
+/* drephip_write_mash_table_rect.  Replaces: the text of
+ * `mash dist <reference.msh> <query.msh>` (the two-file form of
+ * drep/d_cluster.py:569-573): Q x N lines, the query as the outer loop,
+ * "rnames[r]\tqnames[q]\t%g dist\t%g p-value\tcommon/denom\n" of cell
+ * q * N + r of the row-major rectangle (denom NULL = s for every cell), the
+ * distances and p-values the caller's.  No diagonal rule: a query that is also
+ * a reference prints its cell as computed.  Host only; rows formatted on
+ * `threads` threads (0 = all), written in order. */
+int drephip_write_mash_table_rect(const char *path, const char *const *rnames, uint32_t N, const char *const *qnames,
+                                  uint32_t Q, const uint16_t *common, const uint16_t *denom /* nullable */, uint32_t s,
+                                  const double *dist, const double *pval, int threads);
+
 /* ---------------------------------------------------------- primary clustering
  * Replaces: scipy.cluster.hierarchy.linkage(squareform(dist), method) in
  * cluster_hierarchical (drep/d_cluster.py:447-453), called from
