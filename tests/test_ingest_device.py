@@ -4,7 +4,6 @@ that must both agree with it: the oracle's byte-level kseq (oracle.read_fasta
 + a numpy restatement of the layout) and the host packer (drephip_fasta_pack /
 drephip_fasta_info); then the whole drephip_sketch_files and drop-in on the
 device path against the host path and the committed sketches."""
-import ctypes as C
 import glob
 import gzip
 import os
@@ -16,115 +15,9 @@ import pytest
 import oracle
 from drep_amd import _lib, d_cluster
 from drep_amd.mash_io import read_msh
+from ingest_cases import FILL, K, S, _check_all, _device_pack, _expected, _rand_seq, _wrap
 
 pytestmark = pytest.mark.gpu
-S = 1000
-K = 21
-FILL = 0x5A5A5A5A
-
-
-def _np_pack(recs, tile):
-    """numpy restatement of the packed layout (include/drephip.h) for one genome."""
-    span = sum(len(r) for r in recs) + max(len(recs) - 1, 0)
-    P = ((span + 1 + tile - 1) // tile) * tile
-    bases = np.full(P, 255, np.uint8)
-    pos = 0
-    for r in recs:
-        bases[pos:pos + len(r)] = r
-        pos += len(r) + 1
-    lut = np.full(256, 4, np.uint8)
-    for ch, c in zip(b"ACGTacgt", [0, 1, 2, 3, 0, 1, 2, 3]):
-        lut[ch] = c
-    code = lut[bases]
-    ok = code < 4
-    c2 = np.where(ok, code, 0).astype(np.uint32).reshape(-1, 16)
-    codes = (c2 << (2 * np.arange(16, dtype=np.uint32))).sum(axis=1, dtype=np.uint64).astype(np.uint32)
-    v = ok.astype(np.uint32).reshape(-1, 32)
-    valid = (v << np.arange(32, dtype=np.uint32)).sum(axis=1, dtype=np.uint64).astype(np.uint32)
-    return P, codes, valid
-
-
-def _expected(path, tile):
-    """(P, codes, valid, length, n_records, n_kmers) of one file, from the oracle
-    and from the host packer, which must agree with each other."""
-    seq, off, ln = oracle.read_fasta(str(path))
-    recs = [seq[off[i]:off[i + 1]] for i in range(len(off) - 1)]
-    P, want_c, want_v = _np_pack(recs, tile)
-    info = _lib.fasta_info(str(path), K)
-    codes = np.zeros((tile + P) // 16, np.uint32)
-    valid = np.zeros((tile + P) // 32, np.uint32)
-    length, nk = C.c_uint64(0), C.c_uint64(0)
-    assert _lib.lib().drephip_fasta_pack(str(path).encode(), K, codes, valid, tile, tile + P, C.byref(length),
-                                         C.byref(nk)) == 0
-    assert np.array_equal(codes[tile // 16:], want_c) and np.array_equal(valid[tile // 32:], want_v), path
-    assert info["length"] == ln == length.value and info["n_records"] == len(recs) and info["padded"] == P, path
-    assert info["n_kmers"] == nk.value, path
-    return P, want_c, want_v, ln, len(recs), nk.value
-
-
-def _device_pack(ctx, texts, caps=None, gap_tiles=0):
-    """One drephip_fasta_pack_device call over `texts` (bytes each): regions in
-    file order, `gap_tiles` untouched tiles between them, every word of the
-    buffers pre-filled with FILL; the bytes between files are '>' characters,
-    which belong to no file.  Returns (results, codes, valid, base_off, caps)."""
-    import torch
-    tile = _lib.tile_bases()
-    sizes = [len(t) for t in texts]
-    starts, off = _lib.text_layout(sizes)
-    host = np.full(max(int(off[-1]), 16), ord(">"), np.uint8)
-    for t, st in zip(texts, starts):
-        host[int(st):int(st) + len(t)] = np.frombuffer(t, np.uint8)
-    text = torch.from_numpy(host).cuda()
-    if caps is None:
-        caps = [_lib.padded_bases([sz]) for sz in sizes]
-    caps = np.asarray(caps, np.uint64)
-    base = np.zeros(len(texts), np.uint64)
-    at = tile
-    for f in range(len(texts)):
-        base[f] = at
-        at += int(caps[f]) + gap_tiles * tile
-    at += tile
-    codes = torch.full((at // 16,), FILL, dtype=torch.int32, device="cuda")
-    valid = torch.full((at // 32,), FILL, dtype=torch.int32, device="cuda")
-    r = ctx.fasta_pack_device(text, off, base, caps, codes, valid)
-    torch.cuda.synchronize()
-    return r, codes.cpu().numpy().view(np.uint32), valid.cpu().numpy().view(np.uint32), base, caps
-
-
-def _check_all(ctx, texts, tmp_path, tag):
-    """Pack `texts` in one call and hold every file's region and per-file
-    results against the oracle and the host packer; everything outside the
-    regions keeps its fill."""
-    tile = _lib.tile_bases()
-    r, codes, valid, base, caps = _device_pack(ctx, texts)
-    touched_c = np.zeros(len(codes), bool)
-    touched_v = np.zeros(len(valid), bool)
-    for f, t in enumerate(texts):
-        p = tmp_path / ("%s_%02d.fa" % (tag, f))
-        p.write_bytes(t)
-        P, want_c, want_v, ln, nrec, nk = _expected(p, tile)
-        what = (tag, f, t[:60])
-        assert r["status"][f] == 0, what
-        assert (r["length"][f], r["n_records"][f], r["padded"][f], r["n_kmers"][f]) == (ln, nrec, P, nk), what
-        b, cap = int(base[f]), int(caps[f])
-        assert P <= cap, what
-        got_c, got_v = codes[b // 16:(b + cap) // 16], valid[b // 32:(b + cap) // 32]
-        assert np.array_equal(got_v[:P // 32], want_v), what
-        assert np.array_equal(got_c[:P // 16], want_c), what
-        assert not got_c[P // 16:].any() and not got_v[P // 32:].any(), what       # the slack up to cap
-        touched_c[b // 16:(b + cap) // 16] = True
-        touched_v[b // 32:(b + cap) // 32] = True
-    assert (codes[~touched_c] == FILL).all() and (valid[~touched_v] == FILL).all(), tag
-    return r
-
-
-def _rand_seq(rng, n, alphabet=b"ACGT"):
-    a = np.frombuffer(alphabet, np.uint8)
-    return a[rng.integers(0, len(a), n)].tobytes()
-
-
-def _wrap(seq, w):
-    return b"".join(seq[i:i + w] + b"\n" for i in range(0, len(seq), w))
 
 
 # ------------------------------------------------------------------ 1
