@@ -520,6 +520,59 @@ def rect_arrays(qhashes, qnhash, rhashes, rnhash, s: int):
     return tuple(out)
 
 
+def tri_arrays(hashes, nhash, s: int, length=None):
+    """The sketch matrix of an all-pairs call, contiguous: hashes uint64 [N, s],
+    nhash uint32 [N], and with `length` the genome lengths uint64 [N] of a
+    _sig call.  Converts (unlike rect_arrays); ValueError for any other shape."""
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+    nhash = np.ascontiguousarray(nhash, dtype=np.uint32)
+    N = len(nhash)
+    if length is None:
+        if hashes.shape != (N, s):
+            raise ValueError("hashes must be [N, s] = [%d, %d], got %s" % (N, s, hashes.shape))
+        return hashes, nhash
+    length = np.ascontiguousarray(length, dtype=np.uint64)
+    if hashes.shape != (N, s) or length.shape != (N,):
+        raise ValueError("hashes must be [N, s] and length [N]")
+    return hashes, nhash, length
+
+
+def _pairs_cap(pairs: Optional[np.ndarray]) -> int:
+    """Records a caller's `pairs` buffer holds (None: 0, a count-only call)."""
+    if pairs is None:
+        return 0
+    if pairs.dtype != np.uint32 or not pairs.flags.c_contiguous or pairs.ndim != 2 or pairs.shape[1] != 4:
+        raise ValueError("pairs must be a contiguous uint32 [cap, 4] array")
+    return len(pairs)
+
+
+ERR_NOMEM = -4
+
+
+def _nomem_ok(rc: int, what: str) -> int:
+    """A record call's return code: raises on every error but
+    DREPHIP_ERR_NOMEM (the buffer is too small; n_pairs says by how much)."""
+    if rc != ERR_NOMEM:
+        check(rc, what)
+    return rc
+
+
+def _sorted_records(raw_call, what: str, cap: int):
+    """The record calls' retry: raw_call(pairs or None) -> (rc, n) into a
+    buffer of `cap` records, once more with the reported size when that was
+    too small; the records sorted by their two indices, as columns."""
+    buf = np.empty((max(cap, 1), 4), dtype=np.uint32)
+    rc, n = raw_call(buf[:cap] if cap else None)
+    if rc == ERR_NOMEM:
+        buf = np.empty((n, 4), dtype=np.uint32)
+        rc, n = raw_call(buf)
+        check(rc, what)
+    rec = buf[:n]
+    rec = rec[np.lexsort((rec[:, 1], rec[:, 0]))]
+    return (np.ascontiguousarray(rec[:, 0]), np.ascontiguousarray(rec[:, 1]),
+            rec[:, 2].astype(np.uint16), rec[:, 3].astype(np.uint16))
+
+
 class Context:
     """One libdrephip context: a HIP device plus (k, s, seed)."""
 
@@ -829,11 +882,8 @@ class Context:
 
     # -- all-pairs
     def allpairs(self, hashes: np.ndarray, nhash: np.ndarray, want_denom: Optional[bool] = None):
-        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
-        nhash = np.ascontiguousarray(nhash, dtype=np.uint32)
+        hashes, nhash = tri_arrays(hashes, nhash, self.s)
         N = len(nhash)
-        if hashes.shape != (N, self.s):
-            raise ValueError("hashes must be [N, s] = [%d, %d], got %s" % (N, self.s, hashes.shape))
         npairs = N * (N - 1) // 2
         if want_denom is None:
             want_denom = bool((nhash < self.s).any())
@@ -854,11 +904,8 @@ class Context:
                       common_out: np.ndarray, denom_out: Optional[np.ndarray] = None) -> None:
         """Rows [row0, row1) of the triangle into the given condensed segment
         views (uint16, contiguous; length = pairs of those rows)."""
-        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
-        nhash = np.ascontiguousarray(nhash, dtype=np.uint32)
+        hashes, nhash = tri_arrays(hashes, nhash, self.s)
         N = len(nhash)
-        if hashes.shape != (N, self.s):
-            raise ValueError("hashes must be [N, s] = [%d, %d], got %s" % (N, self.s, hashes.shape))
         r1 = min(row1, N - 1)
 
         def start(i):
@@ -875,29 +922,19 @@ class Context:
               "drephip_allpairs_rows")
 
     # -- sparse all-pairs (include/drephip.h: drephip_allpairs_sparse ...)
-    ERR_NOMEM = -4
+    ERR_NOMEM = ERR_NOMEM                # the module's constant, kept as Context.ERR_NOMEM for callers
 
     def allpairs_sparse_raw(self, hashes: np.ndarray, nhash: np.ndarray, row0: int, row1: int,
                             pairs: Optional[np.ndarray]) -> Tuple[int, int]:
         """One drephip_allpairs_sparse call into `pairs` (uint32 [cap, 4],
         contiguous; None: count only): (return code, records the rows hold).
         Raises on every error but DREPHIP_ERR_NOMEM (the buffer is too small)."""
-        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
-        nhash = np.ascontiguousarray(nhash, dtype=np.uint32)
-        N = len(nhash)
-        if hashes.shape != (N, self.s):
-            raise ValueError("hashes must be [N, s] = [%d, %d], got %s" % (N, self.s, hashes.shape))
-        cap = 0
-        if pairs is not None:
-            if pairs.dtype != np.uint32 or not pairs.flags.c_contiguous or pairs.ndim != 2 or pairs.shape[1] != 4:
-                raise ValueError("pairs must be a contiguous uint32 [cap, 4] array")
-            cap = len(pairs)
+        hashes, nhash = tri_arrays(hashes, nhash, self.s)
+        cap = _pairs_cap(pairs)
         n = C.c_uint64(0)
-        rc = lib().drephip_allpairs_sparse(self._h, hashes.reshape(-1), nhash, N, int(row0), int(row1),
+        rc = lib().drephip_allpairs_sparse(self._h, hashes.reshape(-1), nhash, len(nhash), int(row0), int(row1),
                                            pairs.ctypes.data if cap else None, cap, C.byref(n))
-        if rc != self.ERR_NOMEM:
-            check(rc, "drephip_allpairs_sparse")
-        return rc, n.value
+        return _nomem_ok(rc, "drephip_allpairs_sparse"), n.value
 
     def allpairs_sparse(self, hashes: np.ndarray, nhash: np.ndarray, row0: int = 0, row1: Optional[int] = None,
                         cap: Optional[int] = None):
@@ -909,17 +946,8 @@ class Context:
         N = len(nhash)
         row1 = N if row1 is None else int(row1)
         cap = int(cap) if cap is not None else 8 * N + 4096
-        buf = np.empty((max(cap, 1), 4), dtype=np.uint32)
-        rc, n = self.allpairs_sparse_raw(hashes, nhash, row0, row1, buf[:cap] if cap else None)
-        if rc == self.ERR_NOMEM:
-            buf = np.empty((n, 4), dtype=np.uint32)
-            rc, n = self.allpairs_sparse_raw(hashes, nhash, row0, row1, buf)
-            check(rc, "drephip_allpairs_sparse")
-        rec = buf[:n]
-        order = np.lexsort((rec[:, 1], rec[:, 0]))
-        rec = rec[order]
-        return (np.ascontiguousarray(rec[:, 0]), np.ascontiguousarray(rec[:, 1]),
-                rec[:, 2].astype(np.uint16), rec[:, 3].astype(np.uint16))
+        return _sorted_records(lambda pairs: self.allpairs_sparse_raw(hashes, nhash, row0, row1, pairs),
+                               "drephip_allpairs_sparse", cap)
 
     def allpairs_sparse_device(self, d_hashes: int, d_nhash: int, N: int, row0: int, row1: int,
                                d_pairs: Optional[int], cap: int, stream: Optional[int] = None) -> Tuple[int, int]:
@@ -928,9 +956,7 @@ class Context:
         n = C.c_uint64(0)
         rc = lib().drephip_allpairs_sparse_device(self._h, d_hashes, d_nhash, N, row0, row1, d_pairs, cap,
                                                   C.byref(n), stream)
-        if rc != self.ERR_NOMEM:
-            check(rc, "drephip_allpairs_sparse_device")
-        return rc, n.value
+        return _nomem_ok(rc, "drephip_allpairs_sparse_device"), n.value
 
     def allpairs_sparse_device_marked(self, d_hashes: int, d_nhash: int, N: int, row0: int, row1: int,
                                       d_cells: Optional[int], n_cells: int, d_records: Optional[int], n_records: int,
@@ -941,9 +967,7 @@ class Context:
         n = C.c_uint64(0)
         rc = lib().drephip_allpairs_sparse_device_marked(self._h, d_hashes, d_nhash, N, row0, row1, d_cells, n_cells,
                                                          d_records, n_records, d_pairs, cap, C.byref(n), stream)
-        if rc != self.ERR_NOMEM:
-            check(rc, "drephip_allpairs_sparse_device_marked")
-        return rc, n.value
+        return _nomem_ok(rc, "drephip_allpairs_sparse_device_marked"), n.value
 
     # -- query against reference (include/drephip.h: drephip_dist_rect ...)
     def _rect_range(self, Q: int, q0: int, q1: Optional[int]) -> Tuple[int, int]:
@@ -1014,17 +1038,11 @@ class Context:
         qhashes, qnhash, rhashes, rnhash = rect_arrays(qhashes, qnhash, rhashes, rnhash, self.s)
         Q, N = len(qnhash), len(rnhash)
         q0, q1 = self._rect_range(Q, q0, q1)
-        cap = 0
-        if pairs is not None:
-            if pairs.dtype != np.uint32 or not pairs.flags.c_contiguous or pairs.ndim != 2 or pairs.shape[1] != 4:
-                raise ValueError("pairs must be a contiguous uint32 [cap, 4] array")
-            cap = len(pairs)
+        cap = _pairs_cap(pairs)
         n = C.c_uint64(0)
         rc = lib().drephip_dist_rect_sparse(self._h, qhashes.reshape(-1), qnhash, Q, rhashes.reshape(-1), rnhash, N,
                                             q0, q1, pairs.ctypes.data if cap else None, cap, C.byref(n))
-        if rc != self.ERR_NOMEM:
-            check(rc, "drephip_dist_rect_sparse")
-        return rc, n.value
+        return _nomem_ok(rc, "drephip_dist_rect_sparse"), n.value
 
     def dist_rect_sparse_device(self, d_qhashes: int, d_qnhash: int, Q: int, d_rhashes: int, d_rnhash: int, N: int,
                                 q0: int, q1: int, d_pairs: Optional[int], cap: int,
@@ -1034,9 +1052,7 @@ class Context:
         n = C.c_uint64(0)
         rc = lib().drephip_dist_rect_sparse_device(self._h, d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N, q0, q1,
                                                    d_pairs, cap, C.byref(n), stream)
-        if rc != self.ERR_NOMEM:
-            check(rc, "drephip_dist_rect_sparse_device")
-        return rc, n.value
+        return _nomem_ok(rc, "drephip_dist_rect_sparse_device"), n.value
 
     def dist_rect_sparse(self, qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray,
                          q0: int = 0, q1: Optional[int] = None, cap: Optional[int] = None):
@@ -1046,16 +1062,8 @@ class Context:
         for at first (default 8 per query + 4096); when the rows hold more, the
         call is repeated once with the size the library reports."""
         cap = int(cap) if cap is not None else 8 * len(qnhash) + 4096
-        buf = np.empty((max(cap, 1), 4), dtype=np.uint32)
-        rc, n = self.dist_rect_sparse_raw(qhashes, qnhash, rhashes, rnhash, q0, q1, buf[:cap] if cap else None)
-        if rc == self.ERR_NOMEM:
-            buf = np.empty((n, 4), dtype=np.uint32)
-            rc, n = self.dist_rect_sparse_raw(qhashes, qnhash, rhashes, rnhash, q0, q1, buf)
-            check(rc, "drephip_dist_rect_sparse")
-        rec = buf[:n]
-        rec = rec[np.lexsort((rec[:, 1], rec[:, 0]))]
-        return (np.ascontiguousarray(rec[:, 0]), np.ascontiguousarray(rec[:, 1]),
-                rec[:, 2].astype(np.uint16), rec[:, 3].astype(np.uint16))
+        return _sorted_records(lambda pairs: self.dist_rect_sparse_raw(qhashes, qnhash, rhashes, rnhash, q0, q1, pairs),
+                               "drephip_dist_rect_sparse", cap)
 
     def dist_rect_top_raw(self, qhashes: np.ndarray, qnhash: np.ndarray, rhashes: np.ndarray, rnhash: np.ndarray,
                           top: int, q0: int, q1: Optional[int], hits: np.ndarray, count: np.ndarray) -> int:
@@ -1243,21 +1251,15 @@ class Context:
         None: count only) and `pval` (float64 [cap] or None): (return code,
         records that pass the filter, records listed before it).  Raises on
         every error but DREPHIP_ERR_NOMEM."""
-        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
-        nhash = np.ascontiguousarray(nhash, dtype=np.uint32)
-        length = np.ascontiguousarray(length, dtype=np.uint64)
+        hashes, nhash, length = tri_arrays(hashes, nhash, self.s, length)
         N = len(nhash)
-        if hashes.shape != (N, self.s) or length.shape != (N,):
-            raise ValueError("hashes must be [N, s] and length [N]")
         cap = 0 if pairs is None else len(pairs)
         cm = None if cmin is None else np.ascontiguousarray(cmin, dtype=np.uint32)
         n, listed = C.c_uint64(0), C.c_uint64(0)
         rc = lib().drephip_allpairs_sparse_sig(self._h, hashes.reshape(-1), nhash, N, int(row0), int(row1), length,
                                                float(max_p), _ptr(cm), pairs.ctypes.data if cap else None, cap,
                                                _ptr(pval), C.byref(n), C.byref(listed))
-        if rc != self.ERR_NOMEM:
-            check(rc, "drephip_allpairs_sparse_sig")
-        return rc, n.value, listed.value
+        return _nomem_ok(rc, "drephip_allpairs_sparse_sig"), n.value, listed.value
 
     def allpairs_sparse_sig(self, hashes: np.ndarray, nhash: np.ndarray, length: np.ndarray, max_p: float = 1.0,
                             cmin: Optional[np.ndarray] = None, row0: int = 0, row1: Optional[int] = None,
@@ -1266,12 +1268,8 @@ class Context:
         filters applied on the GPU before the copy
         (drephip_allpairs_sparse_sig): (i, j, common, denom, p, n_listed), the
         records sorted by (i, j); n_listed counts them before the filter."""
-        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
-        nhash = np.ascontiguousarray(nhash, dtype=np.uint32)
-        length = np.ascontiguousarray(length, dtype=np.uint64)
+        hashes, nhash, length = tri_arrays(hashes, nhash, self.s, length)
         N = len(nhash)
-        if hashes.shape != (N, self.s) or length.shape != (N,):
-            raise ValueError("hashes must be [N, s] and length [N]")
         row1 = N if row1 is None else int(row1)
 
         def call(ln, *rest):
@@ -1294,9 +1292,7 @@ class Context:
                                                 q0, q1, ql, rl, float(max_p), _ptr(cm),
                                                 pairs.ctypes.data if cap else None, cap, _ptr(pval), C.byref(n),
                                                 C.byref(listed))
-        if rc != self.ERR_NOMEM:
-            check(rc, "drephip_dist_rect_sparse_sig")
-        return rc, n.value, listed.value
+        return _nomem_ok(rc, "drephip_dist_rect_sparse_sig"), n.value, listed.value
 
     def dist_rect_sparse_sig(self, qhashes, qnhash, rhashes, rnhash, qlength, rlength, max_p: float = 1.0,
                              cmin: Optional[np.ndarray] = None, q0: int = 0, q1: Optional[int] = None,

@@ -3,6 +3,7 @@
 // All sketch/dist arithmetic runs in the HIP kernels of sketch.hip and
 // allpairs.hip; the FASTA ingest is ingest_pipeline.cpp.
 #include "ctx.h"
+#include "api_checks.h"
 #include "canon.h"
 #include "ingest_pipeline.h"
 #include "prefilter.h"
@@ -10,7 +11,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -114,17 +114,24 @@ void timing_collect(drephip_ctx *ctx) {
 
 using namespace drephip;
 
-#define GUARD_CTX(ctx)                                              \
-    do {                                                            \
-        if (!(ctx)) { set_error("null context"); return DREPHIP_ERR_ARG; } \
-        HIPC(hipSetDevice((ctx)->device));                          \
-    } while (0)
-
 // Device-pointer entry points run on the caller's stream.  0 is the HIP null
 // stream (also torch's default stream handle), exactly as in the HIP API, so
 // work is ordered after whatever the caller queued there.
 static hipStream_t pick_stream(drephip_ctx *, void *stream) { return (hipStream_t)stream; }
 static void pend_release(drephip_ctx *ctx);
+
+// The call frame's tail ("The C API's call frame"): `impl` runs
+// between timing_begin and timing_collect.  A call that fails leaves its
+// events uncollected; nomem_ok: DREPHIP_ERR_NOMEM (a record form whose buffer
+// is too small) counts as a run that finished, and is returned.
+template <class Impl>
+static int timed(drephip_ctx *ctx, bool nomem_ok, Impl &&impl) {
+    timing_begin(ctx);
+    const int rc = impl();
+    if (rc && !(nomem_ok && rc == DREPHIP_ERR_NOMEM)) return rc;
+    timing_collect(ctx);
+    return rc;
+}
 
 // A deferred sketch (drephip_sketch_device_async) owns the sketch scratch and
 // its status check until drephip_sketch_wait: any other sketch call is refused
@@ -485,13 +492,10 @@ DREPHIP_EXPORT int drephip_sketch_device(drephip_ctx *ctx, const uint32_t *d_cod
     }
     int rc;
     if ((rc = refuse_if_pending(ctx))) return rc;
-    hipStream_t st = pick_stream(ctx, stream);
-    timing_begin(ctx);
-    rc = sketch_device_impl(ctx, d_codes, d_valid, h_base_off, h_padded, h_nkmers, n_genomes, d_hashes,
-                            d_nhash, st);
-    if (rc) return rc;
-    timing_collect(ctx);
-    return DREPHIP_OK;
+    return timed(ctx, false, [&] {
+        return sketch_device_impl(ctx, d_codes, d_valid, h_base_off, h_padded, h_nkmers, n_genomes, d_hashes, d_nhash,
+                                  pick_stream(ctx, stream));
+    });
 }
 
 // Drop a deferred sketch's bookkeeping: its timing events go back to the pool.
@@ -553,11 +557,11 @@ DREPHIP_EXPORT int drephip_sketch_wait(drephip_ctx *ctx, int *redone) {
     // a genome needs another threshold round: rerun the whole call synchronously
     // (finalize left every set empty, so this starts from a clean state)
     const auto off = p.off, pad = p.pad, nk = p.nk;
-    timing_begin(ctx);
-    int rc = sketch_device_impl(ctx, p.d_codes, p.d_valid, off.data(), pad.data(), nk.data(), p.n, p.d_hashes,
-                                p.d_nhash, p.st);
+    int rc = timed(ctx, false, [&] {
+        return sketch_device_impl(ctx, p.d_codes, p.d_valid, off.data(), pad.data(), nk.data(), p.n, p.d_hashes,
+                                  p.d_nhash, p.st);
+    });
     if (rc) return rc;
-    timing_collect(ctx);
     if (redone) *redone = 1;
     return DREPHIP_OK;
 }
@@ -575,12 +579,9 @@ DREPHIP_EXPORT int drephip_allpairs_device(drephip_ctx *ctx, const uint64_t *d_h
                                            uint16_t *d_denom, void *stream) {
     GUARD_CTX(ctx);
     if (!d_hashes || !d_nhash || !d_common) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    timing_begin(ctx);
-    int rc = allpairs_device_impl(ctx, d_hashes, d_nhash, N, row0, row1, d_common, d_denom,
-                                  pick_stream(ctx, stream), false);
-    if (rc) return rc;
-    timing_collect(ctx);
-    return DREPHIP_OK;
+    return timed(ctx, false, [&] {
+        return allpairs_device_impl(ctx, d_hashes, d_nhash, N, row0, row1, d_common, d_denom, pick_stream(ctx, stream), false);
+    });
 }
 
 DREPHIP_EXPORT int drephip_allpairs_device_async(drephip_ctx *ctx, const uint64_t *d_hashes,
@@ -630,12 +631,10 @@ DREPHIP_EXPORT int drephip_screen_part(drephip_ctx *ctx, const uint64_t *d_hashe
     int path;
     int rc = allpairs_geometry(ctx, &R, &path);
     if (rc) return rc;
-    timing_begin(ctx);
-    rc = screen_part_impl(ctx, d_hashes, d_nhash, N, R, part, nparts, pick_stream(ctx, stream), checks, n_cells,
-                          n_records);
-    if (rc) return rc;
-    timing_collect(ctx);
-    return DREPHIP_OK;
+    return timed(ctx, false, [&] {
+        return screen_part_impl(ctx, d_hashes, d_nhash, N, R, part, nparts, pick_stream(ctx, stream), checks, n_cells,
+                                n_records);
+    });
 }
 
 DREPHIP_EXPORT int drephip_screen_part_copy(drephip_ctx *ctx, uint32_t *d_cells, uint32_t *d_records, void *stream) {
@@ -669,13 +668,11 @@ DREPHIP_EXPORT int drephip_allpairs_device_marked(drephip_ctx *ctx, const uint64
     }
     if ((uint64_t)N * ctx->s >= (1ull << 32)) { set_error("the screen needs N x s < 2^32"); return DREPHIP_ERR_UNSUPPORTED; }
     if (ctx->ap_path == DREPHIP_AP_MERGE) { set_error("marks need the table or band path"); return DREPHIP_ERR_ARG; }
-    timing_begin(ctx);
     const ExtMarks marks{(const uint4 *)d_cells, n_cells, (const uint4 *)d_records, n_records};
-    int rc = allpairs_device_impl(ctx, d_hashes, d_nhash, N, row0, row1, d_common, d_denom, pick_stream(ctx, stream),
-                                  false, false, &marks);
-    if (rc) return rc;
-    timing_collect(ctx);
-    return DREPHIP_OK;
+    return timed(ctx, false, [&] {
+        return allpairs_device_impl(ctx, d_hashes, d_nhash, N, row0, row1, d_common, d_denom, pick_stream(ctx, stream),
+                                    false, false, &marks);
+    });
 }
 
 DREPHIP_EXPORT int drephip_allpairs_merge_device(drephip_ctx *ctx, const uint64_t *d_hashes,
@@ -684,11 +681,29 @@ DREPHIP_EXPORT int drephip_allpairs_merge_device(drephip_ctx *ctx, const uint64_
                                                  void *stream) {
     GUARD_CTX(ctx);
     if (!d_hashes || !d_nhash || !d_common) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    timing_begin(ctx);
-    int rc = allpairs_device_impl(ctx, d_hashes, d_nhash, N, row0, row1, d_common, d_denom,
-                                  pick_stream(ctx, stream), true);
-    if (rc) return rc;
-    timing_collect(ctx);
+    return timed(ctx, false, [&] {
+        return allpairs_device_impl(ctx, d_hashes, d_nhash, N, row0, row1, d_common, d_denom, pick_stream(ctx, stream), true);
+    });
+}
+
+// What the triangle's host forms share once their pointers are known not to
+// be null, the counterpart of rect_host_stage: row1 clipped, an empty call
+// told apart (*empty: the form returns at once), the matrix checked and staged
+// onto the context's device (*d_h, *d_n).  The sparse forms (ordered) check
+// the rows, and a _sig form its lengths, before the empty test: an empty call
+// with a bad matrix is refused there, and returns 0 in the dense forms.
+static int tri_host_stage(drephip_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash, const uint64_t *length,
+                          uint32_t N, uint32_t row0, uint32_t *row1, bool ordered, uint64_t **d_h, uint32_t **d_n,
+                          bool *empty) {
+    *empty = !tri_clip(N, row0, row1);
+    int rc;
+    if ((ordered || !*empty) && (rc = check_rows(hashes, nhash, N, ctx->s, ordered))) return rc;
+    if (length && (rc = check_lengths(length, nhash, N))) return rc;
+    if (*empty) return DREPHIP_OK;
+    if ((rc = scratch(ctx, "ap_in_h", (uint64_t)N * ctx->s * 8, (void **)d_h))) return rc;
+    if ((rc = scratch(ctx, "ap_in_n", N * 4ull, (void **)d_n))) return rc;
+    HIPC(hipMemcpyAsync(*d_h, hashes, (uint64_t)N * ctx->s * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemcpyAsync(*d_n, nhash, N * 4ull, hipMemcpyHostToDevice, ctx->stream));
     return DREPHIP_OK;
 }
 
@@ -697,31 +712,18 @@ DREPHIP_EXPORT int drephip_allpairs_merge_device(drephip_ctx *ctx, const uint64_
 static int allpairs_host_rows(drephip_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash, uint32_t N,
                               uint32_t row0, uint32_t row1, uint16_t *common_out, uint16_t *denom_out) {
     if (!hashes || !nhash || !common_out) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    if (row1 > N) row1 = N;
-    if (N < 2 || row0 >= row1 || row0 >= N - 1) return DREPHIP_OK;
-    for (uint32_t i = 0; i < N; i++) {                    // the kernels read rows past nhash: must be padding
-        if (nhash[i] > ctx->s) { set_error("nhash[i] > s"); return DREPHIP_ERR_ARG; }
-        const uint64_t *row = hashes + (uint64_t)i * ctx->s;
-        for (uint32_t j = nhash[i]; j < ctx->s; j++)
-            if (row[j] != ~0ull) { set_error("sketch rows must be UINT64_MAX past nhash[i]"); return DREPHIP_ERR_ARG; }
-    }
-    auto start = [&](uint64_t i) { return i * N - i * (i + 1) / 2; };
-    const uint64_t npairs = start(std::min(row1, N - 1)) - start(row0);
     hipStream_t st = ctx->stream;
     uint64_t *d_h;
     uint32_t *d_n;
     uint16_t *d_c, *d_d = nullptr;
+    bool empty;
     int rc;
-    if ((rc = scratch(ctx, "ap_in_h", (uint64_t)N * ctx->s * 8, (void **)&d_h))) return rc;
-    if ((rc = scratch(ctx, "ap_in_n", N * 4ull, (void **)&d_n))) return rc;
+    if ((rc = tri_host_stage(ctx, hashes, nhash, nullptr, N, row0, &row1, false, &d_h, &d_n, &empty)) || empty) return rc;
+    const uint64_t npairs = tri_pairs(N, row0, row1);
     if ((rc = scratch(ctx, "ap_out_c", npairs * 2, (void **)&d_c))) return rc;
     if (denom_out && (rc = scratch(ctx, "ap_out_d", npairs * 2, (void **)&d_d))) return rc;
-    HIPC(hipMemcpyAsync(d_h, hashes, (uint64_t)N * ctx->s * 8, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(d_n, nhash, N * 4ull, hipMemcpyHostToDevice, st));
-    timing_begin(ctx);
-    rc = allpairs_device_impl(ctx, d_h, d_n, N, row0, row1, d_c, d_d, st, false);
-    if (rc) return rc;
-    timing_collect(ctx);
+    if ((rc = timed(ctx, false, [&] { return allpairs_device_impl(ctx, d_h, d_n, N, row0, row1, d_c, d_d, st, false); })))
+        return rc;
     HIPC(hipMemcpyAsync(common_out, d_c, npairs * 2, hipMemcpyDeviceToHost, st));
     if (denom_out) HIPC(hipMemcpyAsync(denom_out, d_d, npairs * 2, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
@@ -746,12 +748,10 @@ DREPHIP_EXPORT int drephip_allpairs_sparse_device(drephip_ctx *ctx, const uint64
                                                   uint64_t cap, uint64_t *n_pairs, void *stream) {
     GUARD_CTX(ctx);
     if (!d_hashes || !d_nhash || !n_pairs || (cap && !d_pairs)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    timing_begin(ctx);
-    int rc = allpairs_sparse_impl(ctx, d_hashes, d_nhash, N, row0, row1, (uint4 *)d_pairs, cap, n_pairs,
-                                  pick_stream(ctx, stream));
-    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
-    timing_collect(ctx);
-    return rc;
+    return timed(ctx, true, [&] {
+        return allpairs_sparse_impl(ctx, d_hashes, d_nhash, N, row0, row1, (uint4 *)d_pairs, cap, n_pairs,
+                                    pick_stream(ctx, stream));
+    });
 }
 
 DREPHIP_EXPORT int drephip_allpairs_sparse_device_marked(drephip_ctx *ctx, const uint64_t *d_hashes,
@@ -768,50 +768,41 @@ DREPHIP_EXPORT int drephip_allpairs_sparse_device_marked(drephip_ctx *ctx, const
     *n_pairs = 0;
     if ((uint64_t)N * ctx->s >= (1ull << 32)) { set_error("the screen needs N x s < 2^32"); return DREPHIP_ERR_UNSUPPORTED; }
     if (ctx->ap_path == DREPHIP_AP_MERGE) { set_error("marks need the table or band path"); return DREPHIP_ERR_ARG; }
-    timing_begin(ctx);
     const ExtMarks marks{(const uint4 *)d_cells, n_cells, (const uint4 *)d_records, n_records};
-    int rc = allpairs_sparse_impl(ctx, d_hashes, d_nhash, N, row0, row1, (uint4 *)d_pairs, cap, n_pairs,
-                                  pick_stream(ctx, stream), &marks);
-    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
-    timing_collect(ctx);
+    return timed(ctx, true, [&] {
+        return allpairs_sparse_impl(ctx, d_hashes, d_nhash, N, row0, row1, (uint4 *)d_pairs, cap, n_pairs,
+                                    pick_stream(ctx, stream), &marks);
+    });
+}
+
+// The record protocol's last step on the host forms: the first
+// min(n, cap) records, and their p-values where there are any, copied out and
+// the stream waited for; rc -- 0, or DREPHIP_ERR_NOMEM when n > cap -- passes through.
+static int records_out(int rc, const void *d_rec, const double *d_p, uint64_t n, uint64_t cap, uint32_t *pairs,
+                       double *pval, hipStream_t st) {
+    const uint64_t have = std::min(n, cap);
+    if (have) HIPC(hipMemcpyAsync(pairs, d_rec, have * 16, hipMemcpyDeviceToHost, st));
+    if (have && pval) HIPC(hipMemcpyAsync(pval, d_p, have * 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
     return rc;
 }
 
 DREPHIP_EXPORT int drephip_allpairs_sparse(drephip_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash, uint32_t N,
                                            uint32_t row0, uint32_t row1, uint32_t *pairs, uint64_t cap,
                                            uint64_t *n_pairs) {
-    if (!ctx) { set_error("null context"); return DREPHIP_ERR_ARG; }
+    GUARD_CTX(ctx);
     if (!hashes || !nhash || !n_pairs || (cap && !pairs)) { set_error("null argument"); return DREPHIP_ERR_ARG; }
     *n_pairs = 0;
-    const uint32_t s = ctx->s;
-    for (uint32_t i = 0; i < N; i++) {                    // the kernels read whole rows
-        if (nhash[i] > s) { set_error("nhash[i] > s"); return DREPHIP_ERR_ARG; }
-        const uint64_t *row = hashes + (uint64_t)i * s;
-        for (uint32_t j = 1; j < nhash[i]; j++)
-            if (row[j - 1] >= row[j]) { set_error("sketch rows must be ascending and distinct"); return DREPHIP_ERR_ARG; }
-        for (uint32_t j = nhash[i]; j < s; j++)
-            if (row[j] != ~0ull) { set_error("sketch rows must be UINT64_MAX past nhash[i]"); return DREPHIP_ERR_ARG; }
-    }
-    if (row1 > N) row1 = N;
-    if (N < 2 || row0 >= row1 || row0 >= N - 1) return DREPHIP_OK;
-    HIPC(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     uint64_t *d_h;
     uint32_t *d_n, *d_p = nullptr;
+    bool empty;
     int rc;
-    if ((rc = scratch(ctx, "ap_in_h", (uint64_t)N * s * 8, (void **)&d_h))) return rc;
-    if ((rc = scratch(ctx, "ap_in_n", N * 4ull, (void **)&d_n))) return rc;
+    if ((rc = tri_host_stage(ctx, hashes, nhash, nullptr, N, row0, &row1, true, &d_h, &d_n, &empty)) || empty) return rc;
     if (cap && (rc = scratch(ctx, "sp_out", cap * 16, (void **)&d_p))) return rc;
-    HIPC(hipMemcpyAsync(d_h, hashes, (uint64_t)N * s * 8, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(d_n, nhash, N * 4ull, hipMemcpyHostToDevice, st));
-    timing_begin(ctx);
-    rc = allpairs_sparse_impl(ctx, d_h, d_n, N, row0, row1, (uint4 *)d_p, cap, n_pairs, st);
+    rc = timed(ctx, true, [&] { return allpairs_sparse_impl(ctx, d_h, d_n, N, row0, row1, (uint4 *)d_p, cap, n_pairs, st); });
     if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
-    timing_collect(ctx);
-    const uint64_t have = std::min(*n_pairs, cap);
-    if (have) HIPC(hipMemcpyAsync(pairs, d_p, have * 16, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return rc;
+    return records_out(rc, d_p, nullptr, *n_pairs, cap, pairs, nullptr, st);
 }
 
 // ------------------------------------------------- query against reference
@@ -829,11 +820,9 @@ static int rect_dense_device(drephip_ctx *ctx, const RectSets &in, uint32_t q0, 
         set_error("null argument");
         return DREPHIP_ERR_ARG;
     }
-    timing_begin(ctx);
-    int rc = rect_device_impl(ctx, in, q0, q1, d_common, d_denom, pick_stream(ctx, stream), force_merge);
-    if (rc) return rc;
-    timing_collect(ctx);
-    return DREPHIP_OK;
+    return timed(ctx, false, [&] {
+        return rect_device_impl(ctx, in, q0, q1, d_common, d_denom, pick_stream(ctx, stream), force_merge);
+    });
 }
 
 DREPHIP_EXPORT int drephip_dist_rect_device(drephip_ctx *ctx, const uint64_t *d_qhashes, const uint32_t *d_qnhash,
@@ -850,20 +839,6 @@ DREPHIP_EXPORT int drephip_dist_rect_merge_device(drephip_ctx *ctx, const uint64
     return rect_dense_device(ctx, {d_qhashes, d_qnhash, Q, d_rhashes, d_rnhash, N}, q0, q1, d_common, d_denom, stream, true);
 }
 
-// a host sketch matrix as the kernels need it: nhash <= s, rows ascending and
-// distinct, UINT64_MAX past nhash
-static int check_rows(const uint64_t *hashes, const uint32_t *nhash, uint32_t n, uint32_t s) {
-    for (uint32_t i = 0; i < n; i++) {
-        if (nhash[i] > s) { set_error("nhash[i] > s"); return DREPHIP_ERR_ARG; }
-        const uint64_t *row = hashes + (uint64_t)i * s;
-        for (uint32_t j = 1; j < nhash[i]; j++)
-            if (row[j - 1] >= row[j]) { set_error("sketch rows must be ascending and distinct"); return DREPHIP_ERR_ARG; }
-        for (uint32_t j = nhash[i]; j < s; j++)
-            if (row[j] != ~0ull) { set_error("sketch rows must be UINT64_MAX past nhash[i]"); return DREPHIP_ERR_ARG; }
-    }
-    return DREPHIP_OK;
-}
-
 // What the three host forms share once their inputs are known not to be null
 // (each form tests that itself: the tests that go with it differ): q1 clipped,
 // an empty call told apart (*empty: the form returns at once), the form's
@@ -876,7 +851,7 @@ static int rect_host_stage(drephip_ctx *ctx, const RectSets &in, uint32_t q0, ui
     if (*empty) return DREPHIP_OK;
     if (out_null) { set_error("null argument"); return DREPHIP_ERR_ARG; }
     int rc;
-    if ((rc = check_rows(in.qh, in.qn, in.Q, ctx->s)) || (rc = check_rows(in.rh, in.rn, in.N, ctx->s))) return rc;
+    if ((rc = check_rows(in.qh, in.qn, in.Q, ctx->s, true)) || (rc = check_rows(in.rh, in.rn, in.N, ctx->s, true))) return rc;
     const uint64_t qbytes = (uint64_t)in.Q * ctx->s * 8, rbytes = (uint64_t)in.N * ctx->s * 8;
     hipStream_t st = ctx->stream;
     uint64_t *d_qh, *d_rh;
@@ -908,9 +883,7 @@ DREPHIP_EXPORT int drephip_dist_rect(drephip_ctx *ctx, const uint64_t *qhashes, 
     const uint64_t cells = (uint64_t)(q1 - q0) * N;
     if ((rc = scratch(ctx, "rect_out_c", cells * 2, (void **)&d_c))) return rc;
     if (denom_out && (rc = scratch(ctx, "rect_out_d", cells * 2, (void **)&d_d))) return rc;
-    timing_begin(ctx);
-    if ((rc = rect_device_impl(ctx, dev, q0, q1, d_c, d_d, st, false))) return rc;
-    timing_collect(ctx);
+    if ((rc = timed(ctx, false, [&] { return rect_device_impl(ctx, dev, q0, q1, d_c, d_d, st, false); }))) return rc;
     HIPC(hipMemcpyAsync(common_out, d_c, cells * 2, hipMemcpyDeviceToHost, st));
     if (denom_out) HIPC(hipMemcpyAsync(denom_out, d_d, cells * 2, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
@@ -927,11 +900,9 @@ DREPHIP_EXPORT int drephip_dist_rect_sparse_device(drephip_ctx *ctx, const uint6
         set_error("null argument");
         return DREPHIP_ERR_ARG;
     }
-    timing_begin(ctx);
-    int rc = rect_sparse_impl(ctx, in, q0, q1, (uint4 *)d_pairs, cap, n_pairs, pick_stream(ctx, stream));
-    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
-    timing_collect(ctx);
-    return rc;
+    return timed(ctx, true, [&] {
+        return rect_sparse_impl(ctx, in, q0, q1, (uint4 *)d_pairs, cap, n_pairs, pick_stream(ctx, stream));
+    });
 }
 
 DREPHIP_EXPORT int drephip_dist_rect_sparse(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash,
@@ -952,14 +923,9 @@ DREPHIP_EXPORT int drephip_dist_rect_sparse(drephip_ctx *ctx, const uint64_t *qh
     hipStream_t st = ctx->stream;
     uint32_t *d_p = nullptr;
     if (cap && (rc = scratch(ctx, "rect_sp_out", cap * 16, (void **)&d_p))) return rc;
-    timing_begin(ctx);
-    rc = rect_sparse_impl(ctx, dev, q0, q1, (uint4 *)d_p, cap, n_pairs, st);
+    rc = timed(ctx, true, [&] { return rect_sparse_impl(ctx, dev, q0, q1, (uint4 *)d_p, cap, n_pairs, st); });
     if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
-    timing_collect(ctx);
-    const uint64_t have = std::min(*n_pairs, cap);
-    if (have) HIPC(hipMemcpyAsync(pairs, d_p, have * 16, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return rc;
+    return records_out(rc, d_p, nullptr, *n_pairs, cap, pairs, nullptr, st);
 }
 
 // ------------------------------------------------------------ significance
@@ -972,10 +938,24 @@ static int sig_args(drephip_ctx *ctx, double max_p, bool null_arg) {
     return DREPHIP_OK;
 }
 
-// a genome that holds a hash has a length (of at least k)
-static int check_lengths(const uint64_t *length, const uint32_t *nhash, uint32_t n) {
-    for (uint32_t i = 0; i < n; i++)
-        if (nhash[i] && !length[i]) { set_error("a genome with a non-empty sketch has length 0"); return DREPHIP_ERR_ARG; }
+// The record protocol's first half in the two _sig forms: the records counted
+// (`list` with no buffer), room for exactly that many taken ("sig_rec"), the
+// records listed into it and the two counts compared.  list(d_rec, cap, &n) is
+// the form's sparse impl on its staged inputs.
+template <class List>
+static int sig_list(drephip_ctx *ctx, List &&list, uint4 **d_rec, uint64_t *listed) {
+    uint64_t again = 0;
+    *d_rec = nullptr;
+    timing_begin(ctx);
+    int rc = list(nullptr, 0, listed);
+    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
+    if (*listed) {
+        if ((rc = scratch(ctx, "sig_rec", *listed * 16, (void **)d_rec))) return rc;
+        timing_begin(ctx);
+        if ((rc = list(*d_rec, *listed, &again))) return rc;
+        if (again != *listed) { set_error("the record count changed between two runs"); return DREPHIP_ERR_INTERNAL; }
+    }
+    timing_collect(ctx);
     return DREPHIP_OK;
 }
 
@@ -1010,12 +990,7 @@ static int sig_finish(drephip_ctx *ctx, const uint4 *d_rec, uint64_t listed, con
     uint64_t kept = 0;
     if ((rc = records_filter_impl(ctx, d_rec, d_p, listed, max_p, d_cmin, d_out, d_pout, &kept, st))) return rc;
     *n_pairs = kept;
-    const uint64_t have = std::min(kept, cap);
-    if (have) {
-        HIPC(hipMemcpyAsync(pairs, d_out, have * 16, hipMemcpyDeviceToHost, st));
-        if (pval) HIPC(hipMemcpyAsync(pval, d_pout, have * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIPC(hipStreamSynchronize(st));
+    if ((rc = records_out(DREPHIP_OK, d_out, d_pout, kept, cap, pairs, pval, st))) return rc;
     if (kept > cap) { set_error("more records than cap"); return DREPHIP_ERR_NOMEM; }
     return DREPHIP_OK;
 }
@@ -1029,30 +1004,16 @@ DREPHIP_EXPORT int drephip_allpairs_sparse_sig(drephip_ctx *ctx, const uint64_t 
     if ((rc = sig_args(ctx, max_p, !hashes || !nhash || !length || !n_pairs || (cap && !pairs)))) return rc;
     *n_pairs = 0;
     if (n_listed) *n_listed = 0;
-    const uint32_t s = ctx->s;
-    if ((rc = check_rows(hashes, nhash, N, s)) || (rc = check_lengths(length, nhash, N))) return rc;
-    if (row1 > N) row1 = N;
-    if (N < 2 || row0 >= row1 || row0 >= N - 1) return DREPHIP_OK;
     hipStream_t st = ctx->stream;
     uint64_t *d_h;
     uint32_t *d_n;
-    uint4 *d_rec = nullptr;
-    if ((rc = scratch(ctx, "ap_in_h", (uint64_t)N * s * 8, (void **)&d_h))) return rc;
-    if ((rc = scratch(ctx, "ap_in_n", N * 4ull, (void **)&d_n))) return rc;
-    HIPC(hipMemcpyAsync(d_h, hashes, (uint64_t)N * s * 8, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(d_n, nhash, N * 4ull, hipMemcpyHostToDevice, st));
-    // count first, then room for exactly that many
-    uint64_t listed = 0, again = 0;
-    timing_begin(ctx);
-    rc = allpairs_sparse_impl(ctx, d_h, d_n, N, row0, row1, nullptr, 0, &listed, st);
-    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
-    if (listed) {
-        if ((rc = scratch(ctx, "sig_rec", listed * 16, (void **)&d_rec))) return rc;
-        timing_begin(ctx);
-        if ((rc = allpairs_sparse_impl(ctx, d_h, d_n, N, row0, row1, d_rec, listed, &again, st))) return rc;
-        if (again != listed) { set_error("the record count changed between two runs"); return DREPHIP_ERR_INTERNAL; }
-    }
-    timing_collect(ctx);
+    bool empty;
+    if ((rc = tri_host_stage(ctx, hashes, nhash, length, N, row0, &row1, true, &d_h, &d_n, &empty)) || empty) return rc;
+    uint4 *d_rec;
+    uint64_t listed = 0;
+    rc = sig_list(ctx, [&](uint4 *d, uint64_t room, uint64_t *n) {
+        return allpairs_sparse_impl(ctx, d_h, d_n, N, row0, row1, d, room, n, st); }, &d_rec, &listed);
+    if (rc) return rc;
     if (n_listed) *n_listed = listed;
     return sig_finish(ctx, d_rec, listed, length, N, length, N, max_p, cmin, pairs, cap, pval, n_pairs, st);
 }
@@ -1075,18 +1036,11 @@ DREPHIP_EXPORT int drephip_dist_rect_sparse_sig(drephip_ctx *ctx, const uint64_t
     if ((rc = rect_host_stage(ctx, in, q0, &q1, false, &dev, &empty)) || empty) return rc;
     if ((rc = check_lengths(qlength, qnhash, Q)) || (rc = check_lengths(rlength, rnhash, N))) return rc;
     hipStream_t st = ctx->stream;
-    uint4 *d_rec = nullptr;
-    uint64_t listed = 0, again = 0;
-    timing_begin(ctx);
-    rc = rect_sparse_impl(ctx, dev, q0, q1, nullptr, 0, &listed, st);
-    if (rc && rc != DREPHIP_ERR_NOMEM) return rc;
-    if (listed) {
-        if ((rc = scratch(ctx, "sig_rec", listed * 16, (void **)&d_rec))) return rc;
-        timing_begin(ctx);
-        if ((rc = rect_sparse_impl(ctx, dev, q0, q1, d_rec, listed, &again, st))) return rc;
-        if (again != listed) { set_error("the record count changed between two runs"); return DREPHIP_ERR_INTERNAL; }
-    }
-    timing_collect(ctx);
+    uint4 *d_rec;
+    uint64_t listed = 0;
+    rc = sig_list(ctx, [&](uint4 *d, uint64_t room, uint64_t *n) { return rect_sparse_impl(ctx, dev, q0, q1, d, room, n, st); },
+                  &d_rec, &listed);
+    if (rc) return rc;
     if (n_listed) *n_listed = listed;
     return sig_finish(ctx, d_rec, listed, qlength, Q, rlength, N, max_p, cmin, pairs, cap, pval, n_pairs, st);
 }
@@ -1108,10 +1062,7 @@ DREPHIP_EXPORT int drephip_dist_rect_top_device(drephip_ctx *ctx, const uint64_t
     }
     int rc;
     if ((rc = rect_top_args(top))) return rc;
-    timing_begin(ctx);
-    if ((rc = rect_top_impl(ctx, in, q0, q1, top, d_hits, d_count, pick_stream(ctx, stream)))) return rc;
-    timing_collect(ctx);
-    return DREPHIP_OK;
+    return timed(ctx, false, [&] { return rect_top_impl(ctx, in, q0, q1, top, d_hits, d_count, pick_stream(ctx, stream)); });
 }
 
 DREPHIP_EXPORT int drephip_dist_rect_top(drephip_ctx *ctx, const uint64_t *qhashes, const uint32_t *qnhash, uint32_t Q,
@@ -1130,9 +1081,7 @@ DREPHIP_EXPORT int drephip_dist_rect_top(drephip_ctx *ctx, const uint64_t *qhash
     const uint64_t rows = q1 - q0;
     if ((rc = scratch(ctx, "rect_top_hits", rows * top * 16, (void **)&d_h))) return rc;
     if ((rc = scratch(ctx, "rect_top_count", rows * 4, (void **)&d_n))) return rc;
-    timing_begin(ctx);
-    if ((rc = rect_top_impl(ctx, dev, q0, q1, top, d_h, d_n, st))) return rc;
-    timing_collect(ctx);
+    if ((rc = timed(ctx, false, [&] { return rect_top_impl(ctx, dev, q0, q1, top, d_h, d_n, st); }))) return rc;
     HIPC(hipMemcpyAsync(hits, d_h, rows * top * 16, hipMemcpyDeviceToHost, st));
     HIPC(hipMemcpyAsync(count, d_n, rows * 4, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
@@ -1207,10 +1156,6 @@ DREPHIP_EXPORT int drephip_canon_eval(const uint32_t *words, uint64_t n, uint32_
 constexpr uint64_t kSparseMaxCells = 1ull << 31;      // 16 GB
 constexpr uint64_t kSparseMaxPairs = 1ull << 26;      // device pair list: 768 MB
 
-static uint64_t env_u64(const char *name, uint64_t dflt) {
-    if (const char *e = std::getenv(name)) return std::strtoull(e, nullptr, 10);
-    return dflt;
-}
 static uint64_t sparse_cells(const drephip_ctx *ctx) {
     return ctx->link_path == DREPHIP_LINK_PATH_SPARSE ? kSparseMaxCells : env_u64("DREPHIP_LINK_SPARSE_CELLS", 1ull << 28);
 }
@@ -1223,6 +1168,33 @@ static uint64_t sparse_pair_cap(const drephip_ctx *ctx, uint32_t n) {
     const uint64_t cap = ctx->link_path == DREPHIP_LINK_PATH_SPARSE ? kSparseMaxPairs
                                                                     : std::min<uint64_t>(kSparseMaxPairs, 32ull * n + (1ull << 20));
     return std::min(all, cap);
+}
+
+static int linkage_size_ok(uint32_t n) {
+    if (n <= 200000) return DREPHIP_OK;
+    set_error("linkage supports n <= 200000 (n x n f64 matrix in HBM)");
+    return DREPHIP_ERR_UNSUPPORTED;
+}
+
+// The bracket of a linkage call that runs: figures and timing reset, the wall
+// clock started (returned); link_end collects both.
+static double link_begin(drephip_ctx *ctx) {
+    timing_begin(ctx);
+    ctx->link = LinkStats{};
+    return host_now_s();
+}
+static int link_end(drephip_ctx *ctx, double t0) {
+    timing_collect(ctx);
+    ctx->link.wall_s = host_now_s() - t0;
+    return DREPHIP_OK;
+}
+
+// a sparse run (linkage_sparse_impl into ctx->link.sp) that produced Z
+static void link_sparse_done(drephip_ctx *ctx, double matrix_s) {
+    ctx->link.sparse = 1;
+    ctx->link.matrix_s = matrix_s;
+    ctx->link.chain_s = ctx->link.sp.setup_s + ctx->link.sp.chain_s;
+    ctx->link.finish_s = ctx->link.sp.finish_s;
 }
 
 DREPHIP_EXPORT int drephip_set_linkage_path(drephip_ctx *ctx, int path) {
@@ -1245,7 +1217,7 @@ DREPHIP_EXPORT int drephip_linkage_sparse(uint32_t n, uint64_t npairs, const uin
 static int linkage_condensed_sparse(drephip_ctx *ctx, const double *y, uint32_t n, int method, double *Z, int *rc) {
     *rc = DREPHIP_OK;
     if (ctx->link_path == DREPHIP_LINK_PATH_DENSE) return 0;
-    const double t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t0 = host_now_s();
     // the pairs below 1.0, scanned by host threads over row ranges of equal
     // pair counts; any value above 1.0 (or NaN) means no sparse form, more
     // pairs than the cap means the dense path
@@ -1301,16 +1273,13 @@ static int linkage_condensed_sparse(drephip_ctx *ctx, const double *y, uint32_t 
         pj.insert(pj.end(), qj[k].begin(), qj[k].end());
         pv.insert(pv.end(), qv[k].begin(), qv[k].end());
     }
-    const double t1 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t1 = host_now_s();
     const int r = linkage_sparse_impl(n, pi.size(), pi.data(), pj.data(), pv.data(), method, sparse_cells(ctx),
                                       sparse_maxcomp(ctx), Z, &ctx->link.sp,
                                       ctx->link_path == DREPHIP_LINK_PATH_SPARSE ? 1 : 0);
     if (r == DREPHIP_ERR_UNSUPPORTED && ctx->link_path != DREPHIP_LINK_PATH_SPARSE) return 0;
     if (r) { *rc = r; return 0; }
-    ctx->link.sparse = 1;
-    ctx->link.matrix_s = t1 - t0;
-    ctx->link.chain_s = ctx->link.sp.setup_s + ctx->link.sp.chain_s;
-    ctx->link.finish_s = ctx->link.sp.finish_s;
+    link_sparse_done(ctx, t1 - t0);
     return 1;
 }
 
@@ -1318,11 +1287,9 @@ DREPHIP_EXPORT int drephip_linkage(drephip_ctx *ctx, const double *y, uint32_t n
     GUARD_CTX(ctx);
     if (n < 2) return DREPHIP_OK;
     if (!y || !Z) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    if (n > 200000) { set_error("linkage supports n <= 200000 (n x n f64 matrix in HBM)"); return DREPHIP_ERR_UNSUPPORTED; }
-    timing_begin(ctx);
-    ctx->link = LinkStats{};
-    const auto t0 = std::chrono::steady_clock::now();
     int rc;
+    if ((rc = linkage_size_ok(n))) return rc;
+    const double t0 = link_begin(ctx);
     if (!linkage_condensed_sparse(ctx, y, n, method, Z, &rc)) {
         if (rc) return rc;
         double *d_D;
@@ -1331,37 +1298,30 @@ DREPHIP_EXPORT int drephip_linkage(drephip_ctx *ctx, const double *y, uint32_t n
         rc = linkage_device_impl(ctx, d_D, n, method, Z, ctx->stream);
         if (rc) return rc;
     }
-    timing_collect(ctx);
-    ctx->link.wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return DREPHIP_OK;
+    return link_end(ctx, t0);
 }
 
 DREPHIP_EXPORT int drephip_linkage_square(drephip_ctx *ctx, const float *M, uint32_t n, int method, double *Z) {
     GUARD_CTX(ctx);
     if (n < 2) return DREPHIP_OK;
     if (!M || !Z) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    if (n > 200000) { set_error("linkage supports n <= 200000 (n x n f64 matrix in HBM)"); return DREPHIP_ERR_UNSUPPORTED; }
+    int rc;
+    if ((rc = linkage_size_ok(n))) return rc;
     if (method != DREPHIP_LINK_SINGLE && method != DREPHIP_LINK_COMPLETE && method != DREPHIP_LINK_AVERAGE &&
         method != DREPHIP_LINK_WEIGHTED) {
         set_error("linkage method must be single, complete, average or weighted");
         return DREPHIP_ERR_UNSUPPORTED;
     }
-    timing_begin(ctx);
-    ctx->link = LinkStats{};
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = link_begin(ctx);
     double *d_D;
     uint32_t flags = 0;
-    int rc = dist_from_square_impl(ctx, M, n, &d_D, &flags, ctx->stream);
-    if (rc) return rc;
+    if ((rc = dist_from_square_impl(ctx, M, n, &d_D, &flags, ctx->stream))) return rc;
     // scipy's order: squareform's symmetry check, its diagonal check, then linkage's finiteness check
     if (flags & 1) { set_error("Distance matrix 'X' must be symmetric."); return DREPHIP_ERR_ARG; }
     if (flags & 2) { set_error("Distance matrix 'X' diagonal must be zero."); return DREPHIP_ERR_ARG; }
     if (flags & 4) { set_error("The condensed distance matrix must contain only finite values."); return DREPHIP_ERR_ARG; }
-    rc = linkage_device_impl(ctx, d_D, n, method, Z, ctx->stream);
-    if (rc) return rc;
-    timing_collect(ctx);
-    ctx->link.wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return DREPHIP_OK;
+    if ((rc = linkage_device_impl(ctx, d_D, n, method, Z, ctx->stream))) return rc;
+    return link_end(ctx, t0);
 }
 
 DREPHIP_EXPORT int drephip_linkage_counts_device(drephip_ctx *ctx, const uint16_t *d_common, const uint16_t *d_denom,
@@ -1371,26 +1331,14 @@ DREPHIP_EXPORT int drephip_linkage_counts_device(drephip_ctx *ctx, const uint16_
     GUARD_CTX(ctx);
     if (n < 2) return DREPHIP_OK;
     if (!d_common || !perm || !lut || !lut_off || !Z) { set_error("null argument"); return DREPHIP_ERR_ARG; }
-    if (n > 200000) { set_error("linkage supports n <= 200000 (n x n f64 matrix in HBM)"); return DREPHIP_ERR_UNSUPPORTED; }
-    for (uint32_t d = 0; d <= ctx->s; d++)
-        if (lut_off[d] >= 0 && (uint64_t)lut_off[d] + d + 1 > lut_len) { set_error("lut_off/lut_len mismatch"); return DREPHIP_ERR_ARG; }
-    if (!d_denom && lut_off[ctx->s] < 0) {
-        set_error("d_denom is NULL (every denominator is s) but lut_off[s] < 0");
-        return DREPHIP_ERR_ARG;
-    }
-    std::vector<char> seen(n, 0);
-    for (uint32_t i = 0; i < n; i++) {
-        if (perm[i] >= n || seen[perm[i]]) { set_error("perm is not a permutation of 0..n-1"); return DREPHIP_ERR_ARG; }
-        seen[perm[i]] = 1;
-    }
+    int rc;
+    if ((rc = linkage_size_ok(n)) || (rc = check_lut(lut_off, lut_len, ctx->s, d_denom != nullptr)) || (rc = check_perm(perm, n)))
+        return rc;
     // the counts are read after everything the caller queued on `stream`
     // (e.g. the all-pairs call that wrote them, deferred or not)
-    int rc = allpairs_wait_impl(ctx);
-    if (rc) return rc;
+    if ((rc = allpairs_wait_impl(ctx))) return rc;
     HIPC(hipStreamSynchronize(pick_stream(ctx, stream)));
-    timing_begin(ctx);
-    ctx->link = LinkStats{};
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = link_begin(ctx);
     bool done = false;
     if (ctx->link_path != DREPHIP_LINK_PATH_DENSE) {
         // sparse path: the pairs below 1.0 (nonzero counts) extracted on the GPU,
@@ -1407,7 +1355,7 @@ DREPHIP_EXPORT int drephip_linkage_counts_device(drephip_ctx *ctx, const uint16_
             set_error("a pair's denominator has no distance table (lut_off < 0) or its count exceeds it");
             return DREPHIP_ERR_ARG;
         }
-        const double t1 = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        const double t1 = host_now_s() - t0;
         if (!(flags & 2) && np <= cap) {
             std::vector<uint32_t> pi(np), pj(np);
             std::vector<double> pv(np);
@@ -1416,10 +1364,7 @@ DREPHIP_EXPORT int drephip_linkage_counts_device(drephip_ctx *ctx, const uint16_
                                      sparse_maxcomp(ctx), Z, &ctx->link.sp, forced ? 1 : 0);
             if (rc == DREPHIP_OK) {
                 done = true;
-                ctx->link.sparse = 1;
-                ctx->link.matrix_s = t1;
-                ctx->link.chain_s = ctx->link.sp.setup_s + ctx->link.sp.chain_s;
-                ctx->link.finish_s = ctx->link.sp.finish_s;
+                link_sparse_done(ctx, t1);
             } else if (rc != DREPHIP_ERR_UNSUPPORTED || forced) {
                 return rc;
             }
@@ -1436,14 +1381,12 @@ DREPHIP_EXPORT int drephip_linkage_counts_device(drephip_ctx *ctx, const uint16_
         rc = linkage_device_impl(ctx, d_D, n, method, Z, ctx->stream);
         if (rc) return rc;
     }
-    timing_collect(ctx);
-    ctx->link.wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return DREPHIP_OK;
+    return link_end(ctx, t0);
 }
 
 DREPHIP_EXPORT int drephip_linkage_reserve(drephip_ctx *ctx, uint32_t n) {
     GUARD_CTX(ctx);
-    if (n > 200000) { set_error("linkage supports n <= 200000 (n x n f64 matrix in HBM)"); return DREPHIP_ERR_UNSUPPORTED; }
+    if (int rc = linkage_size_ok(n)) return rc;
     if (n < 2) return DREPHIP_OK;
     void *p;
     return scratch(ctx, "lk_D", (uint64_t)n * n * 8, &p);

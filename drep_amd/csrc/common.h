@@ -35,12 +35,16 @@ inline uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
 // DREPHIP_MAX_LAUNCH_ITEMS (tests only) lowers the cap so the split runs at
 // small sizes too.
 constexpr uint64_t kMaxLaunchItems = 1ull << 31;
+// a knob of the environment read as an unsigned decimal (strtoull: 0 for text
+// that is no number); dflt when it is not set
+inline uint64_t env_u64(const char *name, uint64_t dflt) {
+    if (const char *e = std::getenv(name)) return std::strtoull(e, nullptr, 10);
+    return dflt;
+}
 inline uint64_t max_blocks(uint32_t wg) {
     uint64_t cap = kMaxLaunchItems;
-    if (const char *e = std::getenv("DREPHIP_MAX_LAUNCH_ITEMS")) {
-        const uint64_t v = std::strtoull(e, nullptr, 10);
-        if (v) cap = v < 8ull * wg ? 8ull * wg : v > kMaxLaunchItems ? kMaxLaunchItems : v;
-    }
+    if (const uint64_t v = env_u64("DREPHIP_MAX_LAUNCH_ITEMS", 0))
+        cap = v < 8ull * wg ? 8ull * wg : v > kMaxLaunchItems ? kMaxLaunchItems : v;
     return cap / wg / 8 * 8;
 }
 

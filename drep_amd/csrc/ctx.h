@@ -4,6 +4,7 @@
 #include "common.h"
 
 #include <hip/hip_runtime.h>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -259,6 +260,18 @@ namespace drephip {
             return DREPHIP_ERR_HIP;                                                    \
         }                                                                              \
     } while (0)
+
+// The first line of every export that uses the GPU: a context, and its device current.
+#define GUARD_CTX(ctx)                                              \
+    do {                                                            \
+        if (!(ctx)) { ::drephip::set_error("null context"); return DREPHIP_ERR_ARG; } \
+        HIPC(hipSetDevice((ctx)->device));                          \
+    } while (0)
+
+// host wall clock, seconds
+inline double host_now_s() {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 
 // Grow-only named scratch buffer on the context's device.
 int scratch(drephip_ctx *ctx, const char *name, size_t bytes, void **out);

@@ -50,10 +50,7 @@ int sketch_packed_host(drephip_ctx *ctx, const uint32_t *codes, uint64_t n_codes
 }
 
 static uint64_t ingest_batch_bases() {
-    if (const char *e = getenv("DREPHIP_INGEST_BATCH_BASES")) {     // tests: force many batches
-        const uint64_t v = strtoull(e, nullptr, 10);
-        if (v) return v;
-    }
+    if (const uint64_t v = env_u64("DREPHIP_INGEST_BATCH_BASES", 0)) return v;     // tests: force many batches
     return 1ull << 30;                  // ~1 Gbase of sequence per batch
 }
 

@@ -52,10 +52,6 @@
 
 namespace drephip {
 
-static double host_now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 // scipy's _hierarchy_distance_update.pxi, each operation rounded on its own
 static inline double lw_host(int method, double dxi, double dyi, int32_t nx, int32_t ny) {
     if (method == DREPHIP_LINK_COMPLETE) return dxi > dyi ? dxi : (dyi > dxi ? dyi : dxi);

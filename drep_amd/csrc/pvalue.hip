@@ -125,10 +125,8 @@ int records_filter_impl(drephip_ctx *ctx, const uint4 *d_rec, const double *d_pv
     *n_out = 0;
     if (n == 0) return DREPHIP_OK;
     uint64_t chunk = 1ull << 26;
-    if (const char *e = getenv("DREPHIP_FILTER_CHUNK")) {
-        const uint64_t v = strtoull(e, nullptr, 10);
-        if (v >= 1 && v < chunk) chunk = v;
-    }
+    const uint64_t v = env_u64("DREPHIP_FILTER_CHUNK", 0);
+    if (v >= 1 && v < chunk) chunk = v;
     chunk = std::min(chunk, n);
     uint32_t *d_flag, *d_pos, *d_kept, *h_kept;
     void *tmp;
@@ -162,12 +160,6 @@ int records_filter_impl(drephip_ctx *ctx, const uint4 *d_rec, const double *d_pv
 }  // namespace drephip
 
 using namespace drephip;
-
-#define GUARD_CTX(ctx)                                              \
-    do {                                                            \
-        if (!(ctx)) { set_error("null context"); return DREPHIP_ERR_ARG; } \
-        HIPC(hipSetDevice((ctx)->device));                          \
-    } while (0)
 
 DREPHIP_EXPORT int drephip_pvalue_eval(int k, uint32_t s, const uint32_t *common, const uint64_t *len_a,
                                        const uint64_t *len_b, uint64_t n, double *pval, double *r_out,

@@ -1522,8 +1522,7 @@ int screen_part_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint32_t 
     // Row tiles per block of the bitmap: an eighth of the free HBM, as the
     // sparse call's row blocks take (DREPHIP_SCREEN_PART_BLOCK_TILES
     // overrides, tests).  One block is the whole bitmap, ntg x N / 32 words.
-    uint64_t bt = 0;
-    if (const char *e = getenv("DREPHIP_SCREEN_PART_BLOCK_TILES")) bt = strtoull(e, nullptr, 10);
+    uint64_t bt = env_u64("DREPHIP_SCREEN_PART_BLOCK_TILES", 0);
     if (!bt) {
         size_t fr = 0, tot = 0;
         HIPC(hipMemGetInfo(&fr, &tot));
@@ -1721,8 +1720,7 @@ int allpairs_sparse_impl(drephip_ctx *ctx, const uint64_t *d_hashes, const uint3
     uint32_t R = 1;
     int path = DREPHIP_AP_MERGE, rc;
     if ((rc = allpairs_geometry(ctx, &R, &path))) return rc;
-    uint64_t env_rows = 0;
-    if (const char *e = getenv("DREPHIP_SPARSE_BLOCK_ROWS")) env_rows = strtoull(e, nullptr, 10);
+    const uint64_t env_rows = env_u64("DREPHIP_SPARSE_BLOCK_ROWS", 0);
     unsigned long long *d_count;
     uint64_t *h_tot;
     if ((rc = scratch(ctx, "sp_count", 8, (void **)&d_count))) return rc;

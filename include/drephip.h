@@ -258,8 +258,11 @@ int drephip_canon_eval(const uint32_t *words, uint64_t n, uint32_t r, uint32_t *
  * hash count and its denominator.  Distances are a pure function of
  * (common, denom) and are formed on the host (drephip_distance_lut).
  * Input: N rows of s hashes, ascending and distinct; entries past nhash[i] are
- * UINT64_MAX (as drephip_sketch* write them -- the kernels read whole rows;
- * drephip_allpairs checks this, the device entry points assume it). */
+ * UINT64_MAX (as drephip_sketch* write them -- the kernels read whole rows).
+ * drephip_allpairs and drephip_allpairs_rows check nhash[i] <= s and the
+ * UINT64_MAX padding, but not that a row ascends: an unordered row is
+ * accepted and its counts mean nothing.  Every other host form checks all
+ * three; the device entry points assume them. */
 int drephip_allpairs(drephip_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash, uint32_t N,
                      uint16_t *common_out, uint16_t *denom_out /* nullable */);
 

@@ -93,6 +93,20 @@ def test_ingest_pipeline_machinery_on_the_host(tmp_path, sanitize):
     assert ", 0 disagree" in out.stdout and not out.stderr.strip(), out.stdout + out.stderr
 
 
+def test_api_argument_checks_on_the_host(tmp_path):
+    """tools/api_checks_check.cpp: the C API's pure argument checks
+    (csrc/api_checks.h) -- the row check at every nhash with a violation at the
+    first and last position of a row and of the matrix, the triangle's row
+    range against a brute-force pair count, the permutation and distance-table
+    checks -- as a stand-alone host program built with the address and
+    undefined-behaviour sanitizers."""
+    exe = _host_program(tmp_path, os.path.join(ROOT, "tools", "api_checks_check.cpp"), "api_checks_check",
+                        "address,undefined")
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert " checks, 0 disagree" in out.stdout and not out.stderr.strip(), out.stdout + out.stderr
+
+
 def test_set_ingest_path_needs_a_context():
     L = _lib.lib()
     assert L.drephip_set_ingest_path(None, 0) == -1 and L.drephip_last_error()
