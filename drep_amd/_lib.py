@@ -481,8 +481,11 @@ def pivot_fill(codes1: np.ndarray, codes2: np.ndarray, pos1: np.ndarray, pos2: n
     return out
 
 
-# scipy linkage method codes (include/drephip.h DREPHIP_LINK_*)
+# scipy linkage method codes (include/drephip.h DREPHIP_LINK_*): the methods
+# with a sparse form (linkage_sparse), and those of the context's linkage
+# calls -- ward runs on the dense path only
 LINK_METHODS = {"single": 0, "complete": 1, "average": 2, "weighted": 6}
+DENSE_LINK_METHODS = {**LINK_METHODS, "ward": 5}
 
 
 def linkage_sparse(n: int, i: np.ndarray, j: np.ndarray, v: np.ndarray, method: str) -> np.ndarray:
@@ -676,6 +679,7 @@ class Context:
         return dict(zip(("sort", "count", "mark", "lists", "fill"), (float(x) for x in v)))
 
     LINK_METHODS = LINK_METHODS
+    DENSE_LINK_METHODS = DENSE_LINK_METHODS
     # linkage path (include/drephip.h DREPHIP_LINK_PATH_*)
     LINK_AUTO, LINK_DENSE, LINK_SPARSE = 0, 1, 2
 
@@ -691,14 +695,15 @@ class Context:
 
     def linkage(self, y: np.ndarray, method: str) -> np.ndarray:
         """scipy.cluster.hierarchy.linkage(y, method) on the GPU, bit-identical
-        (y: condensed float64 distances)."""
+        (y: condensed float64 distances).  method: single, complete, average,
+        weighted, or ward (dense path only; a negative distance is refused)."""
         y = np.ascontiguousarray(y, dtype=np.float64)
         n = int(round((1 + (1 + 8 * len(y)) ** 0.5) / 2))
         if n * (n - 1) // 2 != len(y):
             raise ValueError("y is not a condensed distance vector")
         Z = np.zeros((max(n - 1, 0), 4), dtype=np.float64)
         if n >= 2:
-            check(lib().drephip_linkage(self._h, y, n, self.LINK_METHODS[method], Z.reshape(-1)),
+            check(lib().drephip_linkage(self._h, y, n, self.DENSE_LINK_METHODS[method], Z.reshape(-1)),
                   "drephip_linkage")
         return Z
 
@@ -712,7 +717,7 @@ class Context:
         n = M.shape[0]
         Z = np.zeros((max(n - 1, 0), 4), dtype=np.float64)
         if n >= 2:
-            check(lib().drephip_linkage_square(self._h, M, n, self.LINK_METHODS[method], Z.reshape(-1)),
+            check(lib().drephip_linkage_square(self._h, M, n, self.DENSE_LINK_METHODS[method], Z.reshape(-1)),
                   "drephip_linkage_square")
         return Z
 
@@ -727,7 +732,7 @@ class Context:
             check(lib().drephip_linkage_counts_device(
                 self._h, d_common, d_denom, n, np.ascontiguousarray(perm, dtype=np.uint32),
                 np.ascontiguousarray(lut, dtype=np.float64), len(lut),
-                np.ascontiguousarray(lut_off, dtype=np.int32), self.LINK_METHODS[method], Z.reshape(-1), stream),
+                np.ascontiguousarray(lut_off, dtype=np.int32), self.DENSE_LINK_METHODS[method], Z.reshape(-1), stream),
                 "drephip_linkage_counts_device")
         return Z
 

@@ -1217,6 +1217,10 @@ DREPHIP_EXPORT int drephip_linkage_sparse(uint32_t n, uint64_t npairs, const uin
 static int linkage_condensed_sparse(drephip_ctx *ctx, const double *y, uint32_t n, int method, double *Z, int *rc) {
     *rc = DREPHIP_OK;
     if (ctx->link_path == DREPHIP_LINK_PATH_DENSE) return 0;
+    if (method == DREPHIP_LINK_WARD) {                 // no sparse form: dense, or refused when sparse is forced
+        if (ctx->link_path == DREPHIP_LINK_PATH_SPARSE) { set_error(kLinkWardSparse); *rc = DREPHIP_ERR_UNSUPPORTED; }
+        return 0;
+    }
     const double t0 = host_now_s();
     // the pairs below 1.0, scanned by host threads over row ranges of equal
     // pair counts; any value above 1.0 (or NaN) means no sparse form, more
@@ -1289,11 +1293,12 @@ DREPHIP_EXPORT int drephip_linkage(drephip_ctx *ctx, const double *y, uint32_t n
     if (!y || !Z) { set_error("null argument"); return DREPHIP_ERR_ARG; }
     int rc;
     if ((rc = linkage_size_ok(n))) return rc;
+    if (!link_method_dense(method)) { set_error(kLinkMethodRefusal); return DREPHIP_ERR_UNSUPPORTED; }
     const double t0 = link_begin(ctx);
     if (!linkage_condensed_sparse(ctx, y, n, method, Z, &rc)) {
         if (rc) return rc;
         double *d_D;
-        rc = dist_from_condensed_impl(ctx, y, n, &d_D, ctx->stream);
+        rc = dist_from_condensed_impl(ctx, y, n, &d_D, ctx->stream, method == DREPHIP_LINK_WARD);
         if (rc) return rc;
         rc = linkage_device_impl(ctx, d_D, n, method, Z, ctx->stream);
         if (rc) return rc;
@@ -1307,11 +1312,7 @@ DREPHIP_EXPORT int drephip_linkage_square(drephip_ctx *ctx, const float *M, uint
     if (!M || !Z) { set_error("null argument"); return DREPHIP_ERR_ARG; }
     int rc;
     if ((rc = linkage_size_ok(n))) return rc;
-    if (method != DREPHIP_LINK_SINGLE && method != DREPHIP_LINK_COMPLETE && method != DREPHIP_LINK_AVERAGE &&
-        method != DREPHIP_LINK_WEIGHTED) {
-        set_error("linkage method must be single, complete, average or weighted");
-        return DREPHIP_ERR_UNSUPPORTED;
-    }
+    if (!link_method_dense(method)) { set_error(kLinkMethodRefusal); return DREPHIP_ERR_UNSUPPORTED; }
     const double t0 = link_begin(ctx);
     double *d_D;
     uint32_t flags = 0;
@@ -1320,6 +1321,7 @@ DREPHIP_EXPORT int drephip_linkage_square(drephip_ctx *ctx, const float *M, uint
     if (flags & 1) { set_error("Distance matrix 'X' must be symmetric."); return DREPHIP_ERR_ARG; }
     if (flags & 2) { set_error("Distance matrix 'X' diagonal must be zero."); return DREPHIP_ERR_ARG; }
     if (flags & 4) { set_error("The condensed distance matrix must contain only finite values."); return DREPHIP_ERR_ARG; }
+    if ((flags & 8) && method == DREPHIP_LINK_WARD) { set_error(kLinkWardNegative); return DREPHIP_ERR_UNSUPPORTED; }
     if ((rc = linkage_device_impl(ctx, d_D, n, method, Z, ctx->stream))) return rc;
     return link_end(ctx, t0);
 }
@@ -1340,7 +1342,11 @@ DREPHIP_EXPORT int drephip_linkage_counts_device(drephip_ctx *ctx, const uint16_
     HIPC(hipStreamSynchronize(pick_stream(ctx, stream)));
     const double t0 = link_begin(ctx);
     bool done = false;
-    if (ctx->link_path != DREPHIP_LINK_PATH_DENSE) {
+    if (method == DREPHIP_LINK_WARD && ctx->link_path == DREPHIP_LINK_PATH_SPARSE) {
+        set_error(kLinkWardSparse);
+        return DREPHIP_ERR_UNSUPPORTED;
+    }
+    if (ctx->link_path != DREPHIP_LINK_PATH_DENSE && method != DREPHIP_LINK_WARD) {
         // sparse path: the pairs below 1.0 (nonzero counts) extracted on the GPU,
         // scipy's algorithm replayed on them on the host (linkage_sparse.cpp)
         const bool forced = ctx->link_path == DREPHIP_LINK_PATH_SPARSE;
@@ -1376,7 +1382,8 @@ DREPHIP_EXPORT int drephip_linkage_counts_device(drephip_ctx *ctx, const uint16_
     }
     if (!done) {
         double *d_D;
-        rc = dist_matrix_impl(ctx, d_common, d_denom, n, perm, lut, lut_len, lut_off, &d_D, ctx->stream);
+        rc = dist_matrix_impl(ctx, d_common, d_denom, n, perm, lut, lut_len, lut_off, &d_D, ctx->stream,
+                              method == DREPHIP_LINK_WARD);
         if (rc) return rc;
         rc = linkage_device_impl(ctx, d_D, n, method, Z, ctx->stream);
         if (rc) return rc;

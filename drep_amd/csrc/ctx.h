@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.h"
+#include "../../include/drephip.h"
 
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -433,13 +434,30 @@ int records_filter_impl(drephip_ctx *ctx, const uint4 *d_rec, const double *d_pv
                         const uint32_t *d_cmin, uint4 *d_out, double *d_pval_out, uint64_t *n_out, hipStream_t st);
 
 // Primary clustering (linkage.hip).
+// the refusal of a method code no path runs (the first sentence is pinned by
+// tests/test_api_contract.py) and of ward on negative input
+constexpr const char *kLinkMethodRefusal =
+    "linkage method must be single, complete, average or weighted, or ward on the dense path";
+constexpr const char *kLinkWardNegative =
+    "ward needs distances >= 0 (scipy's ward gives NaN rows on a negative distance)";
+// (a pair at 1.0 does not stay at 1.0 under ward's update, so the components
+// of the pairs below 1.0 are not independent)
+constexpr const char *kLinkWardSparse = "ward has no sparse form: it runs on the dense path only";
+inline bool link_method_dense(int method) {
+    return method == DREPHIP_LINK_SINGLE || method == DREPHIP_LINK_COMPLETE || method == DREPHIP_LINK_AVERAGE ||
+           method == DREPHIP_LINK_WEIGHTED || method == DREPHIP_LINK_WARD;
+}
 int linkage_device_impl(drephip_ctx *ctx, double *d_D, uint32_t n, int method, double *Z_out, hipStream_t st);
+// the matrix builds: with nonneg (ward) a negative distance among the pairs,
+// found by the kernel that builds the matrix, fails with DREPHIP_ERR_UNSUPPORTED
 int dist_matrix_impl(drephip_ctx *ctx, const uint16_t *d_common, const uint16_t *d_denom, uint32_t n,
                      const uint32_t *perm, const double *lut, uint32_t lut_len, const int32_t *lut_off,
-                     double **d_D_out, hipStream_t st);
-int dist_from_condensed_impl(drephip_ctx *ctx, const double *y, uint32_t n, double **d_D_out, hipStream_t st);
+                     double **d_D_out, hipStream_t st, bool nonneg = false);
+int dist_from_condensed_impl(drephip_ctx *ctx, const double *y, uint32_t n, double **d_D_out, hipStream_t st,
+                             bool nonneg = false);
 // from a host n x n float32 matrix (the pivot's values); *flags: bit 0 not
-// symmetric, bit 1 a nonzero diagonal entry, bit 2 a non-finite value
+// symmetric, bit 1 a nonzero diagonal entry, bit 2 a non-finite value, bit 3 a
+// negative value in the upper triangle
 int dist_from_square_impl(drephip_ctx *ctx, const float *M, uint32_t n, double **d_D_out, uint32_t *flags,
                           hipStream_t st);
 // pairs below 1.0 of the device counts (rows/columns through perm), as (perm i, perm j, lut index) in

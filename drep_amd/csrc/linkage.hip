@@ -150,6 +150,35 @@ __device__ __forceinline__ double lw_update(int method, double dxi, double dyi, 
     return __fma_rn(e, dv.r, q);
 }
 
+// Ward (scipy's _ward): besides the two rows and sizes it takes ni, the size
+// of the other cluster i, and dxy, the distance of the pair being merged.
+//   t = 1.0 / (nx + ny + ni)               (an integer sum, one IEEE division)
+//   sqrt((ni + nx) t dxi dxi + (ni + ny) t dyi dyi - ni t dxy dxy)
+// left to right, every operation rounded on its own, the sums of sizes exact
+// integers.  x and y are reciprocal nearest neighbours, so dxy <= dxi and dxy
+// <= dyi for every live i: on non-negative distances the first term alone is
+// >= the subtracted one (rounding is monotone) and the radicand is >= 0 -- no
+// NaN among the values a decision uses.  A speculated merge that turns out
+// not to be the decision may give one; it loses every compare (all written as
+// v < best) and fmin, and its partials are not used.  The divisor varies per
+// entry, so LwDiv's step-uniform reciprocal does not carry over: the plain
+// division and square root, per entry.
+__device__ __forceinline__ double lw_ward(double dxi, double dyi, double dxy, int32_t nx, int32_t ny, int32_t ni) {
+    const double t = __ddiv_rn(1.0, (double)(nx + ny + ni));
+    const double a = __dmul_rn(__dmul_rn(__dmul_rn((double)(ni + nx), t), dxi), dxi);
+    const double b = __dmul_rn(__dmul_rn(__dmul_rn((double)(ni + ny), t), dyi), dyi);
+    const double c = __dmul_rn(__dmul_rn(__dmul_rn((double)ni, t), dxy), dxy);
+    return __dsqrt_rn(__dsub_rn(__dadd_rn(a, b), c));
+}
+// one update of the step kernels: ward's two more operands are ignored (and
+// fold away) in the other methods' instantiations
+template <int method>
+__device__ __forceinline__ double lw_step(double dxi, double dyi, int32_t nx, int32_t ny, LwDiv dv, int32_t ni,
+                                          double dxy) {
+    if constexpr (method == DREPHIP_LINK_WARD) return lw_ward(dxi, dyi, dxy, nx, ny, ni);
+    else return lw_update(method, dxi, dyi, nx, ny, dv);
+}
+
 // Wave argmin by DPP (row_shr 1/2/4/8 within each 16-lane row, then
 // row_bcast 15/31 across rows: lane 63 ends with the wave's minimum, which
 // readlane broadcasts), in two passes: the minimum value (v_min_f64 of the
@@ -457,6 +486,11 @@ __global__ __launch_bounds__(WG) void k_nn_step(double *__restrict__ D, uint32_t
                                                    LinkCtl *__restrict__ ctl, PartRec *__restrict__ parts,
                                                    double *__restrict__ Z, uint32_t q, int spec_on) {
     __shared__ LinkState sx;
+    // ward: the distance D[top][below] the decision pushed with (dpov), for
+    // the step lanes of a launch that speculates on a pair one of which is
+    // the row y it rewrites (only the ward instantiation references it)
+    __shared__ double sx_dpo;
+    constexpr bool ward = method == DREPHIP_LINK_WARD;
     LinkState *const st = ctl->st;
     LinkFwd *const fwd = ctl->fwd;
     int32_t *const done = &ctl->done;
@@ -651,6 +685,9 @@ __global__ __launch_bounds__(WG) void k_nn_step(double *__restrict__ D, uint32_t
         else if (!X.spec) LK_DIAG(m0);
 #endif
         if (lane0) sx = X;
+        if constexpr (ward) {
+            if (lane0) sx_dpo = dpov;
+        }
         LK_T(ph2);
         if (w0l) {
             if (zmerge) {
@@ -719,6 +756,11 @@ __global__ __launch_bounds__(WG) void k_nn_step(double *__restrict__ D, uint32_t
         const uint4 a = xv[0], b = xv[1], c = xv[2], d = xv[3];
         X = state_from_words(a, b, c, d);
     }
+    double dpo_x = 0.0;                                        // (ward: sx_dpo, wave-uniform)
+    if constexpr (ward) {
+        const uint2 w = *(const uint2 *)&sx_dpo;
+        dpo_x = __longlong_as_double((long long)(((uint64_t)(uint32_t)rfl(w.y) << 32) | (uint32_t)rfl(w.x)));
+    }
     LK_T(ph3);
     if (X.k >= (int32_t)n - 1) return;
     // ---- this step: the pending update of row y fused with the search of row
@@ -760,7 +802,24 @@ __global__ __launch_bounds__(WG) void k_nn_step(double *__restrict__ D, uint32_t
     double xb = fb ? Dx[B + lz] : 0.0, yb = fb ? colY(B) : 0.0;
     double xw = fw ? Dx[W + lz] : 0.0, yw = fw ? colY(W) : 0.0;
     // the sizes of A and B as of this step's decision (for the speculated merge)
-    int32_t rsa = sp ? size[A + lz] : 0, rsb = sp ? size[B + lz] : 0;
+    int32_t rsa = sp || (ward && fa) ? size[A + lz] : 0, rsb = sp ? size[B + lz] : 0;
+    // ward's further operands, uniform loads of words no workgroup of this
+    // launch writes: the size of W (those of A, B, W are the ni of U1[A], U1[B],
+    // U1[W]; workgroup 0's two size stores are overridden as everywhere);
+    // dxy = D[x][y], the distance of the merge being applied (row x is retired
+    // by it: x is not live, so neither copy of the entry is rewritten); and
+    // D[A][B], the speculated pair's distance, where neither is y (only row
+    // and column y are written).  Where one is y, both copies of the entry
+    // are rewritten in this launch (by the y lane and by the other's lane),
+    // so no lane but those may read it: the value after the merge comes
+    // from the decision instead.  A speculating merge launch has y at the
+    // top or below it only through the decision's pushes of the merged row
+    // (spec 2: b, then b's nearest; spec 3: w pushes b back), which carry
+    // that very distance as the next decision's operand (dpo, dpov)
+    int32_t rsw = ward && fw ? size[W + lz] : 0;
+    double dxy = ward && pend ? Dx[y + lz] : 0.0;
+    double dab = ward && sp && !yA && !yB ? Da[B + lz] : 0.0;
+    double dsp = 0.0;                                           // the speculated pair's distance after this merge
     // (as selects: the nested conditional form compiled to exec-mask branches)
     auto size_x = [&](int32_t i, int32_t stored) {
         int32_t s = i == spsb ? spsbsz : stored;               // size_prev
@@ -811,6 +870,7 @@ __global__ __launch_bounds__(WG) void k_nn_step(double *__restrict__ D, uint32_t
         if (first) {
             first = false;
             asm volatile("" : "+v"(xa), "+v"(ya_), "+v"(xb), "+v"(yb), "+v"(xw), "+v"(yw), "+v"(rsa), "+v"(rsb));
+            if constexpr (ward) asm volatile("" : "+v"(rsw), "+v"(dxy), "+v"(dab));
             if (sp) {
                 const int32_t sa = size_x(A, rsa), sb_ = size_x(B, rsb);
                 sxs = A < B ? sa : sb_;
@@ -818,9 +878,10 @@ __global__ __launch_bounds__(WG) void k_nn_step(double *__restrict__ D, uint32_t
                 dvs = lw_div(sxs, sys);
             }
             // (the same bits as those lanes' u: the same operands and update)
-            if (fa) cay = lw_update(method, xa, ya_, nx, ny, dvxy);
-            if (fb) cby = lw_update(method, xb, yb, nx, ny, dvxy);
-            if (fw) cwy = lw_update(method, xw, yw, nx, ny, dvxy);
+            if (fa) cay = lw_step<method>(xa, ya_, nx, ny, dvxy, size_x(A, rsa), dxy);
+            if (fb) cby = lw_step<method>(xb, yb, nx, ny, dvxy, size_x(B, rsb), dxy);
+            if (fw) cwy = lw_step<method>(xw, yw, nx, ny, dvxy, size_x(W, rsw), dxy);
+            if constexpr (ward) dsp = yA || yB ? dpo_x : dab;
         }
 #pragma unroll
         for (int k = 0; k < kLkPer; k++) {
@@ -830,7 +891,8 @@ __global__ __launch_bounds__(WG) void k_nn_step(double *__restrict__ D, uint32_t
             // Written as selects on `live` rather than `continue`s and nested
             // ifs: the branchy form compiled to a cascade of exec-mask branches
             // (~half the pass's instructions at one wave per SIMD)
-            const bool live = i < (int32_t)n && size_x(i, sz[k]) != 0;   // (retires x)
+            const int32_t ni = size_x(i, sz[k]);                         // (ward's third size; y's is nx + ny)
+            const bool live = i < (int32_t)n && ni != 0;                 // (retires x)
             const bool isy = pend && i == y;
             // this launch's merge: row y's new value at i, stored to row and column y
             // (one entry's two copies, D[y][i] and D[i][y])
@@ -855,7 +917,7 @@ __global__ __launch_bounds__(WG) void k_nn_step(double *__restrict__ D, uint32_t
             };
             double u = 0.0;
             if (pend) {
-                u = lw_update(method, dx[k], dy[k], nx, ny, dvxy);
+                u = lw_step<method>(dx[k], dy[k], nx, ny, dvxy, ni, dxy);
                 if (live && !isy) {
                     store_row(i, u);
                     // the column copy D[R][y] of the rows R = A, B, W whose entry y the
@@ -890,7 +952,7 @@ __global__ __launch_bounds__(WG) void k_nn_step(double *__restrict__ D, uint32_t
             if (sp) {
                 // P2: the speculated merged row; P3: W's row after that merge
                 const bool ok = live & (i != A) & (i != B);
-                const double U = lw_update(method, A < B ? ca : cb, A < B ? cb : ca, sxs, sys, dvs);
+                const double U = lw_step<method>(A < B ? ca : cb, A < B ? cb : ca, sxs, sys, dvs, ni, dsp);
                 const bool y_lt = ok & (U < yv);
                 yv = y_lt ? U : yv;
                 yi = y_lt ? i : yi;
@@ -1136,7 +1198,8 @@ constexpr uint32_t kDmT = 64;
 // value of condensed pair t: the reference's float64 distance from the
 // all-pairs counts (lut[off[denom] + common], denom = s when null); a pair
 // whose denominator has no table (off < 0) or whose count exceeds it sets
-// *bad and gets NaN (the host then refuses the result)
+// *bad (bit 0) and gets NaN (the host then refuses the result); a negative
+// value sets bit 1 (ward refuses it)
 struct DmFromCounts {
     const uint16_t *common, *denom;
     uint32_t s;
@@ -1157,23 +1220,31 @@ struct DmFromCounts {
         }
 #pragma unroll
         for (int q = 0; q < R; q++) o[q] = off[dn[q] <= s ? dn[q] : 0];
-        bool anybad = false;
+        bool anybad = false, anyneg = false;
 #pragma unroll
         for (int q = 0; q < R; q++) {
             const bool good = (dn[q] <= s) & (o[q] >= 0) & (cm[q] <= dn[q]);
             const double x = lut[good ? o[q] + cm[q] : 0];
             out[q] = good ? x : __builtin_nan("");
             anybad |= ok[q] & !good;
+            anyneg |= ok[q] & good & (x < 0.0);
         }
         if (anybad) atomicOr(bad, 1u);
+        if (anyneg) atomicOr(bad, 2u);
     }
 };
 struct DmFromCondensed {
     const double *y;
+    uint32_t *neg;                     // nullable: bit 1 set when a pair's value is negative (ward)
     template <int R>
-    __device__ __forceinline__ void batch(const uint64_t (&t)[R], const bool (&)[R], double (&out)[R]) const {
+    __device__ __forceinline__ void batch(const uint64_t (&t)[R], const bool (&ok)[R], double (&out)[R]) const {
+        bool anyneg = false;
 #pragma unroll
-        for (int q = 0; q < R; q++) out[q] = y[t[q]];
+        for (int q = 0; q < R; q++) {
+            out[q] = y[t[q]];
+            anyneg |= ok[q] & (out[q] < 0.0);
+        }
+        if (neg && anyneg) atomicOr(neg, 2u);
     }
 };
 
@@ -1241,7 +1312,8 @@ __global__ __launch_bounds__(256) void k_dist_tiles(V val, uint32_t n, uint32_t 
 // W = M[j0..][i0..]; U[r][c] must equal W[c][r] (==: NaN never does, +0 and
 // -0 do), the diagonal must be 0 and the upper triangle finite.  Both halves
 // of D take the upper value, as squareform keeps only X[i][j], i < j.
-// bad: bit 0 asymmetric, 1 diagonal, 2 non-finite.  HBM-bound: 4 B read and
+// bad: bit 0 asymmetric, 1 diagonal, 2 non-finite, 3 negative (ward refuses
+// it).  HBM-bound: 4 B read and
 // 8 B written per cell.
 __global__ __launch_bounds__(256) void k_square_tiles(const float *__restrict__ M, uint32_t n, uint32_t nb,
                                                       double *__restrict__ D, uint32_t *__restrict__ bad) {
@@ -1267,6 +1339,7 @@ __global__ __launch_bounds__(256) void k_square_tiles(const float *__restrict__ 
             D[(uint64_t)i * n + i] = 0.0;
         } else {
             if (!isfinite(a)) flags |= 4;
+            if (a < 0.0f) flags |= 8;
             D[(uint64_t)i * n + j] = (double)a;
         }
     }
@@ -1301,15 +1374,15 @@ static void launch_nn(int method, dim3 grid, dim3 blk, hipStream_t st, const NnA
                                             a.parts, a.Z, a.q, a.spec_on)
     if (method == DREPHIP_LINK_COMPLETE) DREPHIP_LK_NN(DREPHIP_LINK_COMPLETE);
     else if (method == DREPHIP_LINK_WEIGHTED) DREPHIP_LK_NN(DREPHIP_LINK_WEIGHTED);
+    else if (method == DREPHIP_LINK_WARD) DREPHIP_LK_NN(DREPHIP_LINK_WARD);
     else DREPHIP_LK_NN(DREPHIP_LINK_AVERAGE);
 #undef DREPHIP_LK_NN
 }
 int linkage_device_impl(drephip_ctx *ctx, double *d_D, uint32_t n, int method, double *Z_out, hipStream_t st) {
     if (n < 2) return DREPHIP_OK;
     const double t_chain = now_s();           // chain_s: scratch, graph capture and the steps
-    if (method != DREPHIP_LINK_SINGLE && method != DREPHIP_LINK_COMPLETE && method != DREPHIP_LINK_AVERAGE &&
-        method != DREPHIP_LINK_WEIGHTED) {
-        set_error("linkage method must be single, complete, average or weighted");
+    if (!link_method_dense(method)) {
+        set_error(kLinkMethodRefusal);
         return DREPHIP_ERR_UNSUPPORTED;
     }
     // entries per lane of a step, i.e. the grid density: ~200 workgroups at
@@ -1614,7 +1687,7 @@ int linkage_device_impl(drephip_ctx *ctx, double *d_D, uint32_t n, int method, d
 
 int dist_matrix_impl(drephip_ctx *ctx, const uint16_t *d_common, const uint16_t *d_denom, uint32_t n,
                      const uint32_t *perm, const double *lut, uint32_t lut_len, const int32_t *lut_off,
-                     double **d_D_out, hipStream_t st) {
+                     double **d_D_out, hipStream_t st, bool nonneg) {
     const uint32_t s = ctx->s;
     double *d_D, *d_lut;
     uint32_t *d_perm, *d_bad, *h_bad;
@@ -1639,17 +1712,20 @@ int dist_matrix_impl(drephip_ctx *ctx, const uint16_t *d_common, const uint16_t 
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
-    if (*h_bad) {
+    if (*h_bad & 1) {
         set_error("a pair's denominator has no distance table (lut_off < 0) or its count exceeds it");
         return DREPHIP_ERR_ARG;
     }
+    if (nonneg && (*h_bad & 2)) { set_error(kLinkWardNegative); return DREPHIP_ERR_UNSUPPORTED; }
     ctx->link.matrix_s = now_s() - t1;
     *d_D_out = d_D;
     return DREPHIP_OK;
 }
 
-int dist_from_condensed_impl(drephip_ctx *ctx, const double *y, uint32_t n, double **d_D_out, hipStream_t st) {
+int dist_from_condensed_impl(drephip_ctx *ctx, const double *y, uint32_t n, double **d_D_out, hipStream_t st,
+                             bool nonneg) {
     double *d_D, *d_y;
+    uint32_t *d_bad = nullptr, *h_bad = nullptr;
     int rc;
     const uint64_t np = (uint64_t)n * (n - 1) / 2;
     const double t0 = now_s();
@@ -1657,12 +1733,19 @@ int dist_from_condensed_impl(drephip_ctx *ctx, const double *y, uint32_t n, doub
     const double t1 = now_s();
     ctx->link.alloc_s = t1 - t0;
     if ((rc = scratch(ctx, "lk_y", np * 8, (void **)&d_y))) return rc;
+    if (nonneg) {
+        if ((rc = scratch(ctx, "lk_bad", 4, (void **)&d_bad))) return rc;
+        if ((rc = pinned_host(ctx, "lk_bad", 4, (void **)&h_bad))) return rc;
+        HIPC(hipMemsetAsync(d_bad, 0, 4, st));
+    }
     HIPC(hipMemcpyAsync(d_y, y, np * 8, hipMemcpyHostToDevice, st));
     timing_mark(ctx, 3, st, true);
-    launch_dist_tiles_condensed(DmFromCondensed{d_y}, n, d_D, st);
+    launch_dist_tiles_condensed(DmFromCondensed{d_y, d_bad}, n, d_D, st);
     timing_mark(ctx, 3, st, false);
     HIPC(hipGetLastError());
+    if (nonneg) HIPC(hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
+    if (nonneg && *h_bad) { set_error(kLinkWardNegative); return DREPHIP_ERR_UNSUPPORTED; }
     ctx->link.matrix_s = now_s() - t1;
     *d_D_out = d_D;
     return DREPHIP_OK;

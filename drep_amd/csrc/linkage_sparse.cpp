@@ -551,9 +551,10 @@ int linkage_sparse_impl(uint32_t n, uint64_t np, const uint32_t *pi, const uint3
     I = SparseLinkInfo{};
     I.pairs = np;
     if (n < 2) return DREPHIP_OK;
+    if (method == DREPHIP_LINK_WARD) { set_error(kLinkWardSparse); return DREPHIP_ERR_UNSUPPORTED; }
     if (method != DREPHIP_LINK_SINGLE && method != DREPHIP_LINK_COMPLETE && method != DREPHIP_LINK_AVERAGE &&
         method != DREPHIP_LINK_WEIGHTED) {
-        set_error("linkage method must be single, complete, average or weighted");
+        set_error(kLinkMethodRefusal);
         return DREPHIP_ERR_UNSUPPORTED;
     }
     const double t0 = host_now_s();

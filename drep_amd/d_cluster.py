@@ -619,21 +619,25 @@ def _square_linkage(M: np.ndarray, method: str, gpu: int) -> np.ndarray:
     """scipy.cluster.hierarchy.linkage(squareform(M), method) on the GPU (Z
     bit-identical): float32 M through drephip_linkage_square (squareform's and
     linkage's checks on the device), float64 M through squareform +
-    drephip_linkage.  A failed check raises scipy's ValueError."""
+    drephip_linkage.  A failed check raises scipy's ValueError.  Ward on a
+    negative distance, which the GPU refuses (scipy's ward gives NaN rows
+    there), is run by scipy, so the result is still the reference's."""
     with _lib.Context(device=gpu, k=MASH_K, s=1, seed=MASH_SEED) as ctx:
-        if M.dtype == np.float32:
-            try:
+        try:
+            if M.dtype == np.float32:
                 return ctx.linkage_square(M, method)
-            except _lib.DrepHipError as e:
-                msg = _lib.lib().drephip_last_error().decode("utf-8", "replace")
-                if msg in ("Distance matrix 'X' must be symmetric.", "Distance matrix 'X' diagonal must be zero.",
-                           "The condensed distance matrix must contain only finite values."):
-                    raise ValueError(msg) from e
-                raise
-        y = ssd.squareform(np.asarray(M, dtype=np.float64))
-        if not np.all(np.isfinite(y)):
-            raise ValueError("The condensed distance matrix must contain only finite values.")
-        return ctx.linkage(y, method)
+            y = ssd.squareform(np.asarray(M, dtype=np.float64))
+            if not np.all(np.isfinite(y)):
+                raise ValueError("The condensed distance matrix must contain only finite values.")
+            return ctx.linkage(y, method)
+        except _lib.DrepHipError as e:
+            msg = _lib.lib().drephip_last_error().decode("utf-8", "replace")
+            if msg in ("Distance matrix 'X' must be symmetric.", "Distance matrix 'X' diagonal must be zero.",
+                       "The condensed distance matrix must contain only finite values."):
+                raise ValueError(msg) from e
+            if method == 'ward' and "ward needs distances >= 0" in msg:
+                return scipy.cluster.hierarchy.linkage(ssd.squareform(M), method=method)
+            raise
 
 
 def cluster_mash_database(db, **kwargs):
@@ -643,9 +647,10 @@ def cluster_mash_database(db, **kwargs):
     in-place update of db['dist'] from db['similarity'] as the reference, the
     same pivot (pandas' DataFrame, filled from the category codes by
     libdrephip: _pivot_dist) and the same linkage of its squareform -- run on
-    the GPU for single / complete / average / weighted (scipy's algorithms
-    restated, Z bit-identical; drephip_linkage_square), by scipy for the other
-    methods -- so Cdb, linkage and linkage_db equal the reference's.
+    the GPU for single / complete / average / weighted / ward (scipy's
+    algorithms restated, Z bit-identical; drephip_linkage_square), by scipy for
+    the other methods (centroid, median) and for ward on a negative distance --
+    so Cdb, linkage and linkage_db equal the reference's.
 
     Keyword arguments:
         clusterAlg: how to cluster database (default = single)
@@ -668,7 +673,7 @@ def cluster_mash_database(db, **kwargs):
     link = _Stage('linkage_s')
     link.__enter__()
     try:
-        if (gpu is not None and method in GPU_LINKAGE_METHODS and M.ndim == 2 and M.shape[0] == M.shape[1]
+        if (gpu is not None and method in GPU_DENSE_LINKAGE_METHODS and M.ndim == 2 and M.shape[0] == M.shape[1]
                 and M.shape[0] >= 2 and M.dtype in (np.float32, np.float64)):
             linkage = _square_linkage(M, method, gpu)
         else:
@@ -730,7 +735,10 @@ def linkage_order(names: Sequence[str]) -> np.ndarray:
     return perm
 
 
+# the methods with a sparse form (cluster_mash_sparse), and those of the dense
+# GPU chain: ward's update moves a pair at 1.0, so it has no sparse form
 GPU_LINKAGE_METHODS = ('single', 'complete', 'average', 'weighted')
+GPU_DENSE_LINKAGE_METHODS = GPU_LINKAGE_METHODS + ('ward',)
 
 
 def cluster_mash_condensed(cm: CondensedMash, **kwargs):
@@ -739,14 +747,15 @@ def cluster_mash_condensed(cm: CondensedMash, **kwargs):
 
     The linkage runs on the GPU (libdrephip drephip_linkage_counts_device:
     scipy's nn_chain / MST restated, Z bit-identical; the n x n matrix is
-    built in HBM from the counts) on device `gpu` (default $DREPHIP_DEVICE or
-    0); other methods, or gpu=None, use scipy on the host."""
+    built in HBM from the counts; ward always on that dense chain) on device
+    `gpu` (default $DREPHIP_DEVICE or 0); other methods (centroid, median), or
+    gpu=None, use scipy on the host."""
     P_Lmethod = kwargs.get('clusterAlg', 'single')
     P_Lcutoff = 1 - kwargs.get('P_ani', .9)
     gpu = _linkage_gpu(kwargs)
     names = sorted(cm.names)
     N = len(cm.names)
-    if gpu is not None and P_Lmethod in GPU_LINKAGE_METHODS and N >= 2:
+    if gpu is not None and P_Lmethod in GPU_DENSE_LINKAGE_METHODS and N >= 2:
         import torch
         dev = torch.device('cuda', int(gpu))
         lut, lut_off = linkage_tables(cm.denom, cm.s)

@@ -643,17 +643,10 @@ def synthetic_names(N: int) -> List[str]:
     return ["synthetic_%07d.fna" % i for i in range(N)]
 
 
-def main(argv: Optional[Sequence[str]] = None) -> int:
-    """configs[3] as one job: `python -m torch.distributed.run --nproc-per-node 8
-    --master-addr 127.0.0.1 -m drep_amd.distributed --genomes 100000`
-    (synthetic genomes), or over real FASTA files with --bdb Bdb.csv / --files
-    list.txt (and --data-folder for dRep's cached .msh sketches).  Prints one
-    JSON line (rank 0); --out stores the condensed counts, the primary_linkage
-    pickle and the primary Cdb in drep_amd.store formats."""
+def parse_args(argv=None):
+    """The command line of main().  Refused here, before anything is sketched:
+    --sparse with a linkage method that has no sparse form."""
     import argparse
-    import torch
-    import torch.distributed as dist
-    from . import _lib
     ap = argparse.ArgumentParser()
     ap.add_argument("--genomes", type=int, default=100_000)
     ap.add_argument("--genome-bp", type=int, default=5_000_000)
@@ -675,6 +668,23 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--sparse", action="store_true",
                     help="list only the pairs that share a hash: no condensed vector, no n x n linkage matrix on any rank")
     a = ap.parse_args(argv)
+    if a.sparse and a.method == "ward":
+        ap.error("--sparse --method ward: ward has no sparse form (its update moves a pair at distance 1.0, so the "
+                 "pairs that share no hash cannot be left out); run it without --sparse, on the dense GPU chain")
+    return a
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    """configs[3] as one job: `python -m torch.distributed.run --nproc-per-node 8
+    --master-addr 127.0.0.1 -m drep_amd.distributed --genomes 100000`
+    (synthetic genomes), or over real FASTA files with --bdb Bdb.csv / --files
+    list.txt (and --data-folder for dRep's cached .msh sketches).  Prints one
+    JSON line (rank 0); --out stores the condensed counts, the primary_linkage
+    pickle and the primary Cdb in drep_amd.store formats."""
+    import torch
+    import torch.distributed as dist
+    from . import _lib
+    a = parse_args(argv)
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0)) % max(1, torch.cuda.device_count())

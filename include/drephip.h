@@ -738,11 +738,18 @@ int drephip_write_mash_table_rect(const char *path, const char *const *rnames, u
  * cluster_hierarchical (drep/d_cluster.py:447-453), called from
  * cluster_mash_database (598-630) -- the O(n^2) step of primary clustering.
  * Result: the (n-1) x 4 linkage matrix Z, bit-identical to scipy's (its
- * nn_chain for complete/average/weighted, mst_single_linkage for single,
- * then its stable sort and relabel).  Method codes are scipy's. */
+ * nn_chain for complete/average/weighted/ward, mst_single_linkage for single,
+ * then its stable sort and relabel).  Method codes are scipy's.  Ward runs on
+ * the dense path only (its update moves a pair at 1.0, so the components of
+ * the pairs below 1.0 are not independent: no sparse form) and needs
+ * distances >= 0: a negative entry of y, M or the distance table fails the
+ * call with DREPHIP_ERR_UNSUPPORTED ("ward needs distances >= 0"; scipy
+ * returns NaN rows there).  centroid (3) and median (4) are refused: scipy
+ * runs them through another algorithm (fast_linkage). */
 #define DREPHIP_LINK_SINGLE 0
 #define DREPHIP_LINK_COMPLETE 1
 #define DREPHIP_LINK_AVERAGE 2
+#define DREPHIP_LINK_WARD 5          /* dense path only */
 #define DREPHIP_LINK_WEIGHTED 6
 /* Two paths, chosen per call (drephip_set_linkage_path):
  *  - sparse: when no distance exceeds 1.0 -- Mash's distance of two genomes
@@ -758,7 +765,7 @@ int drephip_write_mash_table_rect(const char *path, const char *const *rnames, u
  *  - dense: the n x n f64 matrix in HBM, one GPU launch per chain step. */
 #define DREPHIP_LINK_PATH_AUTO 0
 #define DREPHIP_LINK_PATH_DENSE 1
-#define DREPHIP_LINK_PATH_SPARSE 2   /* fails (DREPHIP_ERR_UNSUPPORTED) where no sparse form exists */
+#define DREPHIP_LINK_PATH_SPARSE 2   /* fails (DREPHIP_ERR_UNSUPPORTED) where no sparse form exists (ward: always) */
 /* (a new context starts at DREPHIP_LINK_PATH_AUTO, or at the path named by the
  * environment variable DREPHIP_LINK_PATH = auto | dense | sparse) */
 int drephip_set_linkage_path(drephip_ctx *ctx, int path);

@@ -46,11 +46,27 @@ class Sim:
     def active(self):
         return self.size > 0
 
-    def lw(self, dx, dy, nx, ny):       # scipy's Lance-Williams updates and rounding
+    def lw(self, dx, dy, nx, ny, ni=None, dxy=None):
+        """scipy's Lance-Williams updates and rounding.  ward also takes ni, the
+        size of each other cluster (an array beside dx, dy), and dxy, the
+        distance of the merged pair; the other methods ignore them."""
         if self.method == "complete":
             return np.maximum(dx, dy)
         if self.method == "weighted":
             return 0.5 * (dx + dy)
+        if self.method == "ward":
+            # t = 1 / (nx + ny + ni): an integer sum, one division; then left to
+            # right, every operation rounded on its own.  A negative radicand
+            # (retired entries; a speculated pair that turns out not to be
+            # reciprocal) gives NaN, which never wins a minimum on the GPU (its
+            # compares are false): inf here
+            ni = np.asarray(ni, dtype=np.float64)
+            with np.errstate(invalid="ignore"):
+                t = 1.0 / (nx + ny + ni)
+                u = np.sqrt((ni + nx) * t * dx * dx + (ni + ny) * t * dy * dy - ni * t * dxy * dxy)
+            return np.where(np.isnan(u), INF, u)
+        if self.method != "average":
+            raise ValueError("chain_sim: method must be complete, average, weighted or ward")
         return (nx * dx + ny * dy) / float(nx + ny)
 
     def apply_merge(self, a, b):
@@ -59,7 +75,7 @@ class Sim:
         na, nb = size[a], size[b]
         act = self.active().copy()
         act[a] = act[b] = False
-        u = self.lw(D[a], D[b], float(na), float(nb))
+        u = self.lw(D[a], D[b], float(na), float(nb), size, D[a, b])
         D[b, act] = u[act]
         D[act, b] = u[act]
         size[a] = 0
@@ -77,7 +93,7 @@ class Sim:
         x, y = min(t, sb), max(t, sb)
         m = self.active().copy()
         m[t] = m[sb] = False
-        U = self.lw(D[x], D[y], float(size[x]), float(size[y]))
+        U = self.lw(D[x], D[y], float(size[x]), float(size[y]), size, D[x, y])
         p2 = self.rowmin(U, m)
         mw = m.copy()
         mw[w] = False
